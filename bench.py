@@ -9,7 +9,11 @@ Contract: `python bench.py --gpus N --steps K --warmup W`; for N>1 the driver
 launches it under torch.distributed.run with one rank per GPU (RCCL). W
 untimed warmup steps, then exactly K timed steps bracketed by barrier +
 torch.cuda.synchronize on both sides; elapsed is MAX over ranks; rank 0 prints
-ONE JSON line.
+ONE JSON line. A plain run does nothing else. `--dump-outputs DIR` also writes
+the last timed step's loss, logits and updated parameters as DIR/<name>.npy;
+`--full` adds whatever is reported beyond the headline figure.
+`--reproducible` (off by default, implied by `--dump-outputs`) switches the
+conv autotuner off so that a run computes the same thing every time.
 """
 from __future__ import annotations
 
@@ -53,7 +57,55 @@ def parse_args():
     p.add_argument("--image-size", type=int, default=32)
     p.add_argument("--comm-bf16", action="store_true",
                    help="all-reduce gradients in bf16 (half the xGMI bytes)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step computed (loss, logits, updated parameters) "
+                        "as DIR/<name>.npy (rank 0, float32)")
+    p.add_argument("--reproducible", action="store_true",
+                   help="same results run after run: MI355X_AUTOTUNE=0, i.e. "
+                        "the native kernels' launch heuristics instead of "
+                        "choices measured at first use (those flip between "
+                        "near-equal candidates, and MIOpen's wgrad and the "
+                        "atomic wgrad tile sum in scheduling order). Slower "
+                        "than the tuned step; implied by --dump-outputs")
+    p.add_argument("--full", action="store_true",
+                   help="also report everything beyond the headline figure "
+                        "(today: the per-shape conv autotune choices, on "
+                        "stderr); a plain run only sets up, warms up, times "
+                        "the steps and prints the result line")
     return p.parse_args()
+
+
+# --dump-outputs writes at most this much; loss and logits are always whole,
+# the parameter vector is sampled when it alone would not fit.
+DUMP_BUDGET_BYTES = 64 * 1024 * 1024
+DUMP_PARAM_BYTES = 48 * 1024 * 1024
+
+
+def dump_outputs(dirname: str, loss, logits, params) -> None:
+    """Write the last timed step's results as float32 .npy files.
+
+    `params` is the flat concatenation of the model's parameters after the
+    step, in registration order. If it exceeds DUMP_PARAM_BYTES a fixed,
+    seeded sample of its elements (sorted indices, the same for every run
+    with the same model) is written instead.
+    """
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    flat = torch.cat([p.detach().reshape(-1).float().cpu() for p in params])
+    keep = DUMP_PARAM_BYTES // 4
+    if flat.numel() > keep:
+        idx = torch.randint(0, flat.numel(), (keep,),
+                            generator=torch.Generator().manual_seed(0))
+        flat = flat[idx.sort().values]
+    arrays = {"loss": loss.detach().float().reshape(1).cpu(), "params": flat}
+    if logits is not None:  # the graph-captured step returns the loss only
+        arrays["logits"] = logits.detach().float().cpu()
+    total = sum(a.numel() * 4 for a in arrays.values())
+    assert total <= DUMP_BUDGET_BYTES, f"dump of {total} bytes over budget"
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"),
+                a.contiguous().numpy().astype(np.float32, copy=False))
 
 
 def main():
@@ -78,6 +130,10 @@ def main():
     device = torch.device("cuda", local_rank) if torch.cuda.is_available() \
         else torch.device("cpu")
     init_seeds(1 + rank)
+    if args.reproducible or args.dump_outputs:
+        # a dump is there to be compared with another run's, which only
+        # works if both launched the same, order-independent kernels
+        os.environ["MI355X_AUTOTUNE"] = "0"
 
     cfg = TrainConfig(
         arch=args.arch, batch_size=args.global_batch, amp=args.amp,
@@ -119,8 +175,7 @@ def main():
         img_h, lbl_h = batches[i % n_prefab]
         if graph_step is not None:
             # static-buffer copy_ pulls straight from pinned host memory
-            graph_step.run(img_h, lbl_h)
-            return
+            return None, graph_step.run(img_h, lbl_h)
         images = img_h.to(device, non_blocking=True)
         labels = lbl_h.to(device, non_blocking=True)
         if args.channels_last:
@@ -152,6 +207,7 @@ def main():
         else:
             optimizer.step()
         flush_nbt()
+        return out, loss
 
     # --- warmup ------------------------------------------------------------
     from mi355x_ddp.ops.batchnorm import (
@@ -174,8 +230,9 @@ def main():
     if device.type == "cuda":
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = (None, None)  # (logits, loss) of the last timed step
     for i in range(args.steps):
-        one_step(i)
+        last = one_step(i)
     if world > 1:
         dist.barrier()
     if device.type == "cuda":
@@ -190,6 +247,9 @@ def main():
     elapsed = float(t.item())
 
     images_per_sec = args.steps * args.global_batch / elapsed
+    if args.dump_outputs and rank == 0:
+        assert args.steps > 0, "--dump-outputs needs at least one timed step"
+        dump_outputs(args.dump_outputs, last[1], last[0], model.parameters())
     if rank == 0:
         arch_label = {"resnet18": "ResNet18", "resnet34": "ResNet34",
                       "resnet50": "ResNet50", "resnet101": "ResNet101",
@@ -197,7 +257,8 @@ def main():
                       "resnet18_imagenet": "ResNet18-ImageNet",
                       "resnet50_imagenet": "ResNet50-ImageNet"}.get(
                           args.arch, args.arch)
-        data_label = "CIFAR-100" if args.image_size == 32 else             f"synthetic-{args.image_size}px"
+        data_label = "CIFAR-100" if args.image_size == 32 else \
+            f"synthetic-{args.image_size}px"
         result = {
             "metric": f"images/sec, {arch_label} {data_label} DDP training",
             "value": round(images_per_sec, 1),
@@ -226,6 +287,10 @@ def main():
                 "sync_bn": cfg.sync_bn,
                 "grad_accu_steps": args.grad_accu_steps,
                 "mode": args.mode,
+                # False under --reproducible / --dump-outputs: such a run's
+                # figure is not the tuned headline
+                "conv_autotune":
+                os.environ.get("MI355X_AUTOTUNE", "1") == "1",
                 "seconds_per_epoch": round(EPOCH_IMAGES / images_per_sec, 4)
                 if args.image_size == 32 else None,
                 "reference_seconds_per_epoch_4x2080ti":
@@ -234,7 +299,7 @@ def main():
             },
         }
         print(json.dumps(result), flush=True)
-        if os.environ.get("MI355X_TUNE_REPORT", "0") == "1":
+        if args.full or os.environ.get("MI355X_TUNE_REPORT", "0") == "1":
             from mi355x_ddp.ops.conv import tune_report
             print("[autotune choices]\n" + tune_report(), file=sys.stderr,
                   flush=True)

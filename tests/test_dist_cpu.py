@@ -313,13 +313,25 @@ def _check_bf16_comm_parity(rank, world):
         assert torch.allclose(p.grad, rp.grad, atol=2e-3, rtol=2e-2), \
             (p.grad - rp.grad).abs().max()
 
-    # reduce_flat path too
-    wrapped.zero_grad_buffer()
-    wrapped(xs[rank]).pow(2).mean().backward()
-    wrapped.reduce_flat()
-    gathered = [torch.zeros_like(wrapped.flat_grads) for _ in range(world)]
-    dist.all_gather(gathered, wrapped.flat_grads)
+    # reduce_flat path too. It is the hook-free path (overlap=False, as the
+    # graph-captured step builds it): on a wrapper with overlap hooks,
+    # backward would already have bucket all-reduces in flight on comm_grads
+    # when reduce_flat() copies into it, and the ranks' results would depend
+    # on thread timing.
+    torch.manual_seed(42)
+    flat_model = nn.Sequential(nn.Linear(8, 16), nn.ReLU(), nn.Linear(16, 4))
+    flat = FlatDDP(flat_model, bucket_cap_mb=1e-5,
+                   comm_dtype=torch.bfloat16, overlap=False)
+    assert flat.comm_grads is not None
+    flat.zero_grad_buffer()
+    flat(xs[rank]).pow(2).mean().backward()
+    flat.reduce_flat()
+    gathered = [torch.zeros_like(flat.flat_grads) for _ in range(world)]
+    dist.all_gather(gathered, flat.flat_grads)
     assert torch.allclose(gathered[0], gathered[1])  # ranks agree exactly
+    for p, rp in zip(flat_model.parameters(), ref_model.parameters()):
+        assert torch.allclose(p.grad, rp.grad, atol=2e-3, rtol=2e-2), \
+            (p.grad - rp.grad).abs().max()
 
 
 def test_bf16_comm_parity(free_port):

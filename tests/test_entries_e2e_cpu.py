@@ -80,6 +80,43 @@ def test_bench_multirank_contract(tmp_path, free_port):
     assert rec["value"] > 0 and rec["unit"] == "images/sec"
 
 
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's loss, logits and updated
+    parameters as float32 .npy; --full is accepted and keeps the single
+    result line; two runs with the same arguments see identical inputs, so
+    on CPU (no autotune, fixed reduction order) their dumps agree."""
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="4")
+    dumps = []
+    for tag, extra in (("a", []), ("b", ["--full"])):
+        out_dir = tmp_path / tag
+        r = subprocess.run(
+            [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+             "--steps", "2", "--warmup", "1", "--global-batch", "16",
+             "--amp", "fp32", "--dump-outputs", str(out_dir)] + extra,
+            cwd=tmp_path, env=env, capture_output=True, text=True,
+            timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        assert sorted(p.name for p in out_dir.iterdir()) == \
+            ["logits.npy", "loss.npy", "params.npy"]
+        dumps.append({n: np.load(out_dir / f"{n}.npy")
+                      for n in ("loss", "logits", "params")})
+    a, b = dumps
+    assert a["loss"].shape == (1,) and a["logits"].shape == (16, 100)
+    assert a["params"].ndim == 1 and a["params"].size > 10_000_000
+    total = 0
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all(), n
+        total += a[n].nbytes
+        # same seeds, same inputs, same arithmetic: fp32 rounding noise only
+        np.testing.assert_allclose(a[n], b[n], rtol=1e-5, atol=1e-6)
+    assert total <= 64 * 1024 * 1024
+
+
 def test_resume_from_checkpoint(tmp_path, free_port):
     """Train 1 epoch, then resume into a 2-epoch run from the final
     checkpoint (reference only documented the rank-0 save pattern;

@@ -190,6 +190,39 @@ def test_bench_single_gpu_contract():
     assert r["n_gpus"] == 1 and r["steps"] == 5
     assert r["value"] > 0 and r["higher_is_better"] is True
     assert r["unit"] == "images/sec"
+    # ms_per_step is the time of one timed step; value derives from it
+    assert r["ms_per_step"] > 0
+    assert abs(r["value"] * r["ms_per_step"] / 1000 / 256 - 1) < 1e-2
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """Two --dump-outputs runs with the same arguments compute the same
+    thing: the dump switches the conv autotuner off, and the native kernels
+    at their launch heuristics hold none that accumulates with atomics, so
+    logits and updated parameters are bit-identical; the scalar loss is
+    summed over rows with atomicAdd, so it may differ in its last bits (a few
+    float32 ulps: 1e-6 relative)."""
+    import numpy as np
+    dumps = []
+    for tag in ("a", "b"):
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--steps", "3", "--warmup", "1",
+             "--dump-outputs", str(tmp_path / tag)],
+            capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert sorted(p.name for p in (tmp_path / tag).iterdir()) == \
+            ["logits.npy", "loss.npy", "params.npy"]
+        dumps.append({n: np.load(tmp_path / tag / f"{n}.npy")
+                      for n in ("loss", "logits", "params")})
+    a, b = dumps
+    # the last timed step's results, float32, within the 64 MB budget
+    assert a["loss"].shape == (1,) and a["logits"].shape == (256, 100)
+    for arr in a.values():
+        assert arr.dtype == np.float32 and np.isfinite(arr).all()
+    assert sum(arr.nbytes for arr in a.values()) <= 64 * 1024 * 1024
+    assert np.array_equal(a["logits"], b["logits"])
+    assert np.array_equal(a["params"], b["params"])
+    np.testing.assert_allclose(a["loss"], b["loss"], rtol=1e-6, atol=0)
 
 
 @pytest.mark.parametrize("arch", ["resnet34", "resnet50"])
