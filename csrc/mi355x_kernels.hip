@@ -491,6 +491,95 @@ __global__ void bn_finalize_kernel(const float* __restrict__ packed,
   }
 }
 
+// Forward tail: partial [split][2C] -> stats [4][C] = {mean, invstd, scale,
+// shift} (+ running stats update) in ONE launch, replacing the
+// bn_reduce_partials -> bn_finalize -> bn_coeffs chain. Block c folds the sum
+// and sqsum columns of channel c in bn_reduce_partials_kernel's order (thread-
+// strided j loop at 256 threads, then block_reduce_sum) and thread 0 applies
+// the bn_finalize_kernel / bn_coeffs_kernel expressions unchanged, so the
+// results are bit-identical to the three-kernel chain. split == 1 (a packed
+// [2C] after the SyncBN all_reduce) is the degenerate case of the same loop.
+__global__ void bn_fwd_tail_kernel(const float* __restrict__ partial,
+                                   const float* __restrict__ weight,
+                                   const float* __restrict__ bias,
+                                   float* __restrict__ stats,  // [4][C]
+                                   float* __restrict__ running_mean,
+                                   float* __restrict__ running_var,
+                                   float count, float momentum, float eps,
+                                   int split, int C) {
+  __shared__ float lds[32];
+  const int c = blockIdx.x;
+  const int twoC = 2 * C;
+  float s = 0.f, sq = 0.f;
+  for (int j = threadIdx.x; j < split; j += blockDim.x) {
+    s += partial[(long)j * twoC + c];
+    sq += partial[(long)j * twoC + C + c];
+  }
+  s = block_reduce_sum(s, lds);
+  __syncthreads();
+  sq = block_reduce_sum(sq, lds);
+  if (threadIdx.x != 0) return;
+  const float mean = s / count;
+  float var = sq / count - mean * mean;
+  var = fmaxf(var, 0.f);
+  const float invstd = rsqrtf(var + eps);
+  if (running_mean != nullptr) {
+    const float unbiased = var * (count / fmaxf(count - 1.f, 1.f));
+    running_mean[c] += momentum * (mean - running_mean[c]);
+    running_var[c] += momentum * (unbiased - running_var[c]);
+  }
+  const float sc = weight[c] * invstd;
+  stats[c] = mean;
+  stats[C + c] = invstd;
+  stats[2 * C + c] = sc;
+  stats[3 * C + c] = bias[c] - mean * sc;
+}
+
+// Backward tail: partial [split][2C] -> sums [2][C] = {sum_dy, sum_dy_xhat}
+// (dbeta, dgamma of the local batch) and, in the same launch, either the
+// bn_bwd_coeffs_kernel fold into coeffs [3][C] = {A, B, D}, or (DUP) a second
+// copy of the sums as packed [2C] for the SyncBN all_reduce to overwrite.
+// Reduction order as in bn_fwd_tail_kernel.
+template <bool DUP>
+__global__ void bn_bwd_tail_kernel(const float* __restrict__ partial,
+                                   const float* __restrict__ weight,
+                                   const float* __restrict__ mean,
+                                   const float* __restrict__ invstd,
+                                   float inv_count, bool training,
+                                   float* __restrict__ sums,  // [2][C]
+                                   float* __restrict__ out,   // [3][C] | [2C]
+                                   int split, int C) {
+  __shared__ float lds[32];
+  const int c = blockIdx.x;
+  const int twoC = 2 * C;
+  float sdy = 0.f, sdyx = 0.f;
+  for (int j = threadIdx.x; j < split; j += blockDim.x) {
+    sdy += partial[(long)j * twoC + c];
+    sdyx += partial[(long)j * twoC + C + c];
+  }
+  sdy = block_reduce_sum(sdy, lds);
+  __syncthreads();
+  sdyx = block_reduce_sum(sdyx, lds);
+  if (threadIdx.x != 0) return;
+  sums[c] = sdy;
+  sums[C + c] = sdyx;
+  if (DUP) {
+    out[c] = sdy;
+    out[C + c] = sdyx;
+    return;
+  }
+  const float is = invstd[c];
+  const float a = weight[c] * is;
+  float b = 0.f, dd = 0.f;
+  if (training) {
+    b = -a * is * sdyx * inv_count;
+    dd = -a * sdy * inv_count - b * mean[c];
+  }
+  out[c] = a;
+  out[C + c] = b;
+  out[2 * C + c] = dd;
+}
+
 template <typename scalar_t, bool RELU>
 __global__ void bn_bwd_reduce_nhwc_v2_kernel(const scalar_t* __restrict__ dy,
                                              const scalar_t* __restrict__ x,
@@ -1028,7 +1117,87 @@ inline int split_for_nhwc(long P, int rpb) {
   long avail = (P + rpb - 1) / rpb;
   return (int)std::min((long)512, std::min(want, avail));
 }
+inline bool takes_v2(const at::Tensor& x) {
+  return is_clast(x) && v2_ok((int)x.size(1), (int)x.element_size());
+}
+
+// Half/BFloat16-only dispatch for the 16-byte-vector kernels.
+template <typename F>
+inline void dispatch_16bit(const at::Tensor& t, const char* name, F&& f) {
+  if (t.scalar_type() == at::kBFloat16) f(at::BFloat16{});
+  else if (t.scalar_type() == at::kHalf) f(at::Half{});
+  else TORCH_CHECK(false, name, ": expected a Half or BFloat16 tensor");
+}
+
+// The v2 stats launch alone: per-block partial [split][2C], not yet reduced
+// over split (bn_reduce_partials_kernel or a tail kernel does that).
+at::Tensor stats_partial_v2(const at::Tensor& x) {
+  const int C = x.size(1);
+  const long P = x.numel() / C;
+  const int tpr = C / 8, rpb = 256 / tpr;
+  const int split = split_for_nhwc(P, rpb);
+  auto partial = at::empty({split, 2L * C}, x.options().dtype(at::kFloat));
+  dispatch_16bit(x, "bn_stats_partial", [&](auto tag) {
+    using scalar_t = decltype(tag);
+    hipLaunchKernelGGL(bn_stats_nhwc_v2_kernel<scalar_t>,
+                       dim3(1, split), dim3(256), 0, cur_stream(),
+                       x.data_ptr<scalar_t>(), partial.data_ptr<float>(),
+                       P, C, tpr);
+  });
+  return partial;
+}
+
+at::Tensor bwd_reduce_partial_v2(const at::Tensor& dy, const at::Tensor& x,
+                                 const at::Tensor& mean,
+                                 const at::Tensor& invstd,
+                                 const at::Tensor& y, bool relu) {
+  const int C = x.size(1);
+  const long P = x.numel() / C;
+  const int tpr = C / 8, rpb = 256 / tpr;
+  const int split = split_for_nhwc(P, rpb);
+  auto partial = at::empty({split, 2L * C}, x.options().dtype(at::kFloat));
+  dispatch_16bit(x, "bn_bwd_reduce_partial", [&](auto tag) {
+    using scalar_t = decltype(tag);
+    auto launch = [&](auto relu_c) {
+      hipLaunchKernelGGL((bn_bwd_reduce_nhwc_v2_kernel<scalar_t,
+                                                       decltype(relu_c)::value>),
+                         dim3(1, split), dim3(256), 0, cur_stream(),
+                         dy.data_ptr<scalar_t>(), x.data_ptr<scalar_t>(),
+                         y.data_ptr<scalar_t>(), mean.data_ptr<float>(),
+                         invstd.data_ptr<float>(), partial.data_ptr<float>(),
+                         P, C, tpr);
+    };
+    relu ? launch(std::true_type{}) : launch(std::false_type{});
+  });
+  return partial;
+}
+
+at::Tensor reduce_partials(const at::Tensor& partial) {
+  const int split = partial.size(0);
+  const long twoC = partial.size(1);
+  auto packed = at::empty({twoC}, partial.options());
+  hipLaunchKernelGGL(bn_reduce_partials_kernel,
+                     dim3((int)twoC), dim3(256), 0, cur_stream(),
+                     partial.data_ptr<float>(), packed.data_ptr<float>(),
+                     split, (int)twoC);
+  return packed;
+}
 }  // namespace
+
+// True when x takes the NHWC v2 stats/reduce kernels, i.e. when
+// bn_stats_partial / bn_bwd_reduce_partial and the tail kernels apply.
+bool bn_v2_ok(at::Tensor x) {
+  return x.is_cuda() && x.dim() == 4 && takes_v2(x);
+}
+
+// Per-block {sum, sqsum} partial [split][2C] of the v2 path, unreduced:
+// bn_fwd_tail folds it. bn_stats_packed(x) is this plus the reduce launch.
+at::Tensor bn_stats_partial(at::Tensor x) {
+  CHECK_CUDA(x); check_dense(x, "x");
+  TORCH_CHECK(takes_v2(x), "bn_stats_partial: x must take the NHWC v2 path "
+              "(see bn_v2_ok)");
+  return stats_partial_v2(x);
+}
 
 // Per-channel {sum, sqsum} packed into ONE [2C] fp32 tensor (the layout the
 // SyncBN all_reduce and bn_finalize consume).
@@ -1041,20 +1210,7 @@ at::Tensor bn_stats_packed(at::Tensor x) {
   AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::Half, at::ScalarType::BFloat16,
       x.scalar_type(), "bn_stats_packed", [&] {
     if (is_clast(x) && v2_ok(C, (int)sizeof(scalar_t))) {
-      const long P = (long)N * S;
-      const int tpr = C / 8, rpb = 256 / tpr;
-      const int split = split_for_nhwc(P, rpb);
-      auto partial = at::empty({split, 2L * C}, opts);
-      hipLaunchKernelGGL(bn_stats_nhwc_v2_kernel<scalar_t>,
-                         dim3(1, split), dim3(256), 0, cur_stream(),
-                         x.data_ptr<scalar_t>(), partial.data_ptr<float>(),
-                         P, C, tpr);
-      auto packed = at::empty({2L * C}, opts);
-      hipLaunchKernelGGL(bn_reduce_partials_kernel,
-                         dim3(2 * C), dim3(256), 0, cur_stream(),
-                         partial.data_ptr<float>(), packed.data_ptr<float>(),
-                         split, 2 * C);
-      result = packed;
+      result = reduce_partials(stats_partial_v2(x));
     } else if (is_clast(x)) {
       const long P = (long)N * S;
       auto packed = at::zeros({2L * C}, opts);
@@ -1097,6 +1253,52 @@ std::vector<at::Tensor> bn_finalize(at::Tensor packed, double count,
   return {mean, invstd};
 }
 
+namespace {
+// partial is [split][2C], or a packed [2C] (split = 1)
+inline void check_partial(const at::Tensor& partial, int* split, int* C) {
+  CHECK_CUDA(partial); CHECK_CONTIG(partial);
+  TORCH_CHECK(partial.scalar_type() == at::kFloat &&
+              (partial.dim() == 1 || partial.dim() == 2) &&
+              partial.size(-1) % 2 == 0,
+              "partial must be fp32 [split][2C] or [2C]");
+  *split = partial.dim() == 2 ? (int)partial.size(0) : 1;
+  *C = (int)(partial.size(-1) / 2);
+}
+inline const float* chan_ptr(const at::Tensor& t, int C, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+              t.scalar_type() == at::kFloat && t.numel() == C,
+              name, " must be a contiguous fp32 HIP tensor of C elements");
+  return t.data_ptr<float>();
+}
+}  // namespace
+
+// partial {sum,sqsum} [split][2C] (or packed [2C]) -> {stats, mean, invstd}:
+// stats is fp32 [4][C] = {mean, invstd, scale, shift} for bn_fwd_apply; mean
+// and invstd are its first two rows as views. Updates running stats in
+// place when given. One launch: reduce + finalize + coefficient fold.
+std::vector<at::Tensor> bn_fwd_tail(at::Tensor partial, at::Tensor weight,
+                                    at::Tensor bias, double count,
+                                    double momentum, double eps,
+                                    c10::optional<at::Tensor> running_mean,
+                                    c10::optional<at::Tensor> running_var) {
+  int split, C;
+  check_partial(partial, &split, &C);
+  const float* w = chan_ptr(weight, C, "weight");
+  const float* b = chan_ptr(bias, C, "bias");
+  TORCH_CHECK(running_mean.has_value() == running_var.has_value(),
+              "running_mean and running_var go together");
+  float* rm = running_mean ?
+      const_cast<float*>(chan_ptr(*running_mean, C, "running_mean")) : nullptr;
+  float* rv = running_var ?
+      const_cast<float*>(chan_ptr(*running_var, C, "running_var")) : nullptr;
+  auto stats = at::empty({4, C}, partial.options());
+  hipLaunchKernelGGL(bn_fwd_tail_kernel, dim3(C), dim3(256), 0, cur_stream(),
+                     partial.data_ptr<float>(), w, b, stats.data_ptr<float>(),
+                     rm, rv, (float)count, (float)momentum, (float)eps,
+                     split, C);
+  return {stats, stats.select(0, 0), stats.select(0, 1)};
+}
+
 // {sum_dy, sum_dy_xhat} packed [2C], relu mask folded in.
 at::Tensor bn_bwd_reduce_packed(at::Tensor dy, at::Tensor x, at::Tensor mean,
                                 at::Tensor invstd, at::Tensor y, bool relu) {
@@ -1109,26 +1311,8 @@ at::Tensor bn_bwd_reduce_packed(at::Tensor dy, at::Tensor x, at::Tensor mean,
   AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::Half, at::ScalarType::BFloat16,
       x.scalar_type(), "bn_bwd_reduce_packed", [&] {
     if (is_clast(x) && v2_ok(C, (int)sizeof(scalar_t))) {
-      const long P = (long)N * S;
-      const int tpr = C / 8, rpb = 256 / tpr;
-      const int split = split_for_nhwc(P, rpb);
-      auto partial = at::empty({split, 2L * C}, opts);
-      auto launch = [&](auto relu_c) {
-        hipLaunchKernelGGL((bn_bwd_reduce_nhwc_v2_kernel<scalar_t,
-                                                         decltype(relu_c)::value>),
-                           dim3(1, split), dim3(256), 0, cur_stream(),
-                           dy.data_ptr<scalar_t>(), x.data_ptr<scalar_t>(),
-                           y.data_ptr<scalar_t>(), mean.data_ptr<float>(),
-                           invstd.data_ptr<float>(), partial.data_ptr<float>(),
-                           P, C, tpr);
-      };
-      relu ? launch(std::true_type{}) : launch(std::false_type{});
-      auto packed = at::empty({2L * C}, opts);
-      hipLaunchKernelGGL(bn_reduce_partials_kernel,
-                         dim3(2 * C), dim3(256), 0, cur_stream(),
-                         partial.data_ptr<float>(), packed.data_ptr<float>(),
-                         split, 2 * C);
-      result = packed;
+      result = reduce_partials(
+          bwd_reduce_partial_v2(dy, x, mean, invstd, y, relu));
     } else if (is_clast(x)) {
       const long P = (long)N * S;
       auto packed = at::zeros({2L * C}, opts);
@@ -1164,6 +1348,127 @@ at::Tensor bn_bwd_reduce_packed(at::Tensor dy, at::Tensor x, at::Tensor mean,
   return result;
 }
 
+// Per-block {sum_dy, sum_dy_xhat} partial [split][2C] of the v2 path,
+// unreduced: bn_bwd_tail folds it. bn_bwd_reduce_packed is this plus the
+// reduce launch.
+at::Tensor bn_bwd_reduce_partial(at::Tensor dy, at::Tensor x, at::Tensor mean,
+                                 at::Tensor invstd, at::Tensor y, bool relu) {
+  CHECK_CUDA(dy); check_dense(dy, "dy"); check_dense(x, "x");
+  TORCH_CHECK(takes_v2(x), "bn_bwd_reduce_partial: x must take the NHWC v2 "
+              "path (see bn_v2_ok)");
+  TORCH_CHECK(is_clast(dy) && dy.sizes() == x.sizes() &&
+              dy.scalar_type() == x.scalar_type(), "dy/x mismatch");
+  if (relu) {
+    TORCH_CHECK(is_clast(y) && y.sizes() == x.sizes() &&
+                y.scalar_type() == x.scalar_type(), "y/x mismatch");
+  }
+  const int C = x.size(1);
+  chan_ptr(mean, C, "mean");
+  chan_ptr(invstd, C, "invstd");
+  return bwd_reduce_partial_v2(dy, x, mean, invstd, y, relu);
+}
+
+// partial [split][2C] -> {dbeta, dgamma, coeffs}: dbeta = sum_dy and dgamma =
+// sum_dy_xhat are the two rows of one fresh fp32 [2][C] tensor (views, no
+// copy); coeffs is fp32 [3][C] = {A, B, D} for bn_bwd_apply. One launch:
+// reduce + backward coefficient fold.
+std::vector<at::Tensor> bn_bwd_tail(at::Tensor partial, at::Tensor weight,
+                                    at::Tensor mean, at::Tensor invstd,
+                                    double inv_count, bool training) {
+  int split, C;
+  check_partial(partial, &split, &C);
+  const float* w = chan_ptr(weight, C, "weight");
+  const float* mu = chan_ptr(mean, C, "mean");
+  const float* is = chan_ptr(invstd, C, "invstd");
+  auto sums = at::empty({2, C}, partial.options());
+  auto coeffs = at::empty({3, C}, partial.options());
+  hipLaunchKernelGGL(bn_bwd_tail_kernel<false>, dim3(C), dim3(256), 0,
+                     cur_stream(), partial.data_ptr<float>(), w, mu, is,
+                     (float)inv_count, training, sums.data_ptr<float>(),
+                     coeffs.data_ptr<float>(), split, C);
+  return {sums.select(0, 0), sums.select(0, 1), coeffs};
+}
+
+// SyncBN variant: no coefficients (they need the cross-rank sums); the sums
+// are written twice instead, {dbeta, dgamma} rows for the local grads and
+// packed [2C] for the all_reduce to overwrite.
+std::vector<at::Tensor> bn_bwd_tail_dup(at::Tensor partial) {
+  int split, C;
+  check_partial(partial, &split, &C);
+  auto sums = at::empty({2, C}, partial.options());
+  auto packed = at::empty({2L * C}, partial.options());
+  hipLaunchKernelGGL(bn_bwd_tail_kernel<true>, dim3(C), dim3(256), 0,
+                     cur_stream(), partial.data_ptr<float>(), nullptr, nullptr,
+                     nullptr, 0.f, false, sums.data_ptr<float>(),
+                     packed.data_ptr<float>(), split, C);
+  return {sums.select(0, 0), sums.select(0, 1), packed};
+}
+
+namespace {
+// y = x*scale[c] + shift[c] (+res)(relu): the bn_fwd_vec_kernel launch alone.
+void launch_bn_fwd_vec(const at::Tensor& x, const at::Tensor& residual,
+                       bool has_res, at::Tensor& y, const float* sc,
+                       const float* sh, bool relu) {
+  const int N = x.size(0), C = x.size(1);
+  const int S = x.numel() / ((long)N * C);
+  const bool clast = is_clast(x);
+  const long nvec = x.numel() / 8;
+  const int vblocks = (int)std::min((nvec + 255) / 256, (long)2048);
+  dispatch_16bit(x, "bn_fwd", [&](auto tag) {
+    using scalar_t = decltype(tag);
+    auto launch = [&](auto relu_c, auto res_c, auto cl_c) {
+      hipLaunchKernelGGL((bn_fwd_vec_kernel<scalar_t, decltype(relu_c)::value,
+                                            decltype(res_c)::value,
+                                            decltype(cl_c)::value>),
+                         dim3(vblocks), dim3(256), 0, cur_stream(),
+                         x.data_ptr<scalar_t>(),
+                         has_res ? residual.data_ptr<scalar_t>() : nullptr,
+                         y.data_ptr<scalar_t>(), sc, sh, nvec, C, S);
+    };
+    auto l2 = [&](auto relu_c, auto res_c) {
+      clast ? launch(relu_c, res_c, std::true_type{})
+            : launch(relu_c, res_c, std::false_type{});
+    };
+    if (relu && has_res) l2(std::true_type{}, std::true_type{});
+    else if (relu) l2(std::true_type{}, std::false_type{});
+    else if (has_res) l2(std::false_type{}, std::true_type{});
+    else l2(std::false_type{}, std::false_type{});
+  });
+}
+inline bool bn_vec_ok(const at::Tensor& x) {
+  const int N = x.size(0), C = x.size(1);
+  const long S = x.numel() / ((long)N * C);
+  return x.element_size() == 2 && x.numel() % 8 == 0 &&
+         (is_clast(x) ? (C % 8 == 0) : (S % 8 == 0));
+}
+}  // namespace
+
+// Forward apply from precomputed coefficients: stats is bn_fwd_tail's fp32
+// [4][C] (rows 2, 3 = scale, shift). Launches only bn_fwd_vec_kernel.
+at::Tensor bn_fwd_apply(at::Tensor x, at::Tensor stats, bool relu,
+                        c10::optional<at::Tensor> residual_opt) {
+  const at::Tensor residual = residual_opt ? *residual_opt : at::Tensor();
+  CHECK_CUDA(x); check_dense(x, "x");
+  TORCH_CHECK(x.dim() == 4 && bn_vec_ok(x),
+              "bn_fwd_apply: x must take the vectorised path");
+  const int C = x.size(1);
+  TORCH_CHECK(stats.is_cuda() && stats.is_contiguous() &&
+              stats.scalar_type() == at::kFloat && stats.dim() == 2 &&
+              stats.size(0) == 4 && stats.size(1) == C,
+              "stats must be fp32 [4][C]");
+  const bool has_res = residual.defined() && residual.numel() > 0;
+  if (has_res) {
+    TORCH_CHECK(is_clast(residual) == is_clast(x) &&
+                residual.sizes() == x.sizes() &&
+                residual.scalar_type() == x.scalar_type(),
+                "residual layout mismatch");
+  }
+  auto y = at::empty_like(x);
+  const float* sc = stats.data_ptr<float>() + 2L * C;
+  launch_bn_fwd_vec(x, residual, has_res, y, sc, sc + C, relu);
+  return y;
+}
+
 at::Tensor bn_fwd(at::Tensor x, at::Tensor weight, at::Tensor bias,
                   at::Tensor mean, at::Tensor invstd, bool relu,
                   at::Tensor residual) {
@@ -1180,30 +1485,20 @@ at::Tensor bn_fwd(at::Tensor x, at::Tensor weight, at::Tensor bias,
   auto wf = weight.to(at::kFloat).contiguous();
   auto bf = bias.to(at::kFloat).contiguous();
   const int blocks = (int)std::min((total + 1023) / 1024, (long)4096);
-  const bool vec_ok = (total % 8 == 0) &&
-      (clast ? (C % 8 == 0) : (S % 8 == 0));
+  if (bn_vec_ok(x)) {
+    auto coeffs = at::empty({2, C}, x.options().dtype(at::kFloat));
+    float* sc = coeffs.data_ptr<float>();
+    float* sh = sc + C;
+    hipLaunchKernelGGL(bn_coeffs_kernel, dim3((C + 255) / 256), dim3(256),
+                       0, cur_stream(), wf.data_ptr<float>(),
+                       bf.data_ptr<float>(), mean.data_ptr<float>(),
+                       invstd.data_ptr<float>(), sc, sh, C);
+    launch_bn_fwd_vec(x, residual, has_res, y, sc, sh, relu);
+    return y;
+  }
   AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::Half, at::ScalarType::BFloat16,
       x.scalar_type(), "bn_fwd", [&] {
     auto launch = [&](auto relu_c, auto res_c, auto cl_c) {
-      if (vec_ok && sizeof(scalar_t) == 2) {
-        auto coeffs = at::empty({2, C}, x.options().dtype(at::kFloat));
-        float* sc = coeffs.data_ptr<float>();
-        float* sh = sc + C;
-        hipLaunchKernelGGL(bn_coeffs_kernel, dim3((C + 255) / 256), dim3(256),
-                           0, cur_stream(), wf.data_ptr<float>(),
-                           bf.data_ptr<float>(), mean.data_ptr<float>(),
-                           invstd.data_ptr<float>(), sc, sh, C);
-        const long nvec = total / 8;
-        const int vblocks = (int)std::min((nvec + 255) / 256, (long)2048);
-        hipLaunchKernelGGL((bn_fwd_vec_kernel<scalar_t, decltype(relu_c)::value,
-                                              decltype(res_c)::value,
-                                              decltype(cl_c)::value>),
-                           dim3(vblocks), dim3(256), 0, cur_stream(),
-                           x.data_ptr<scalar_t>(),
-                           has_res ? residual.data_ptr<scalar_t>() : nullptr,
-                           y.data_ptr<scalar_t>(), sc, sh, nvec, C, S);
-        return;
-      }
       hipLaunchKernelGGL((bn_fwd_kernel<scalar_t, decltype(relu_c)::value,
                                         decltype(res_c)::value,
                                         decltype(cl_c)::value>),
@@ -1269,6 +1564,78 @@ std::vector<at::Tensor> bn_bwd_reduce(at::Tensor dy, at::Tensor x,
   return {sum_dy, sum_dy_xhat};
 }
 
+namespace {
+// dx = A*g + B*x + D (+ dres): the bn_bwd_vec_kernel launch alone. A points
+// at the contiguous [3][C] {A, B, D} table.
+void launch_bn_bwd_vec(const at::Tensor& dy, const at::Tensor& x,
+                       const at::Tensor& y, at::Tensor& dx, at::Tensor& dres,
+                       const float* A, bool relu, bool training,
+                       bool need_dres) {
+  const int N = x.size(0), C = x.size(1);
+  const int S = x.numel() / ((long)N * C);
+  const bool clast = is_clast(x);
+  const float* B = A + C;
+  const float* D = B + C;
+  const long nvec = x.numel() / 8;
+  const int vblocks = (int)std::min((nvec + 255) / 256, (long)2048);
+  dispatch_16bit(x, "bn_bwd", [&](auto tag) {
+    using scalar_t = decltype(tag);
+    auto launch = [&](auto relu_c, auto train_c, auto dres_c, auto cl_c) {
+      hipLaunchKernelGGL((bn_bwd_vec_kernel<scalar_t, decltype(relu_c)::value,
+                                            decltype(train_c)::value,
+                                            decltype(dres_c)::value,
+                                            decltype(cl_c)::value>),
+                         dim3(vblocks), dim3(256), 0, cur_stream(),
+                         dy.data_ptr<scalar_t>(), x.data_ptr<scalar_t>(),
+                         y.data_ptr<scalar_t>(), dx.data_ptr<scalar_t>(),
+                         need_dres ? dres.data_ptr<scalar_t>() : nullptr,
+                         A, B, D, nvec, C, S);
+    };
+    auto l3 = [&](auto relu_c, auto train_c, auto dres_c) {
+      clast ? launch(relu_c, train_c, dres_c, std::true_type{})
+            : launch(relu_c, train_c, dres_c, std::false_type{});
+    };
+    auto l2 = [&](auto relu_c, auto train_c) {
+      need_dres ? l3(relu_c, train_c, std::true_type{})
+                : l3(relu_c, train_c, std::false_type{});
+    };
+    if (relu) {
+      training ? l2(std::true_type{}, std::true_type{})
+               : l2(std::true_type{}, std::false_type{});
+    } else {
+      training ? l2(std::false_type{}, std::true_type{})
+               : l2(std::false_type{}, std::false_type{});
+    }
+  });
+}
+}  // namespace
+
+// Backward apply from precomputed coefficients: coeffs is bn_bwd_tail's fp32
+// [3][C] = {A, B, D}. Launches only bn_bwd_vec_kernel. Returns {dx, dres}.
+std::vector<at::Tensor> bn_bwd_apply(at::Tensor dy, at::Tensor x, at::Tensor y,
+                                     at::Tensor coeffs, bool relu,
+                                     bool training, bool need_dres) {
+  CHECK_CUDA(dy); check_dense(dy, "dy"); check_dense(x, "x");
+  TORCH_CHECK(x.dim() == 4 && bn_vec_ok(x),
+              "bn_bwd_apply: x must take the vectorised path");
+  TORCH_CHECK(is_clast(dy) == is_clast(x) && dy.sizes() == x.sizes() &&
+              dy.scalar_type() == x.scalar_type(), "dy/x mismatch");
+  if (relu) {
+    TORCH_CHECK(is_clast(y) == is_clast(x) && y.sizes() == x.sizes() &&
+                y.scalar_type() == x.scalar_type(), "y/x mismatch");
+  }
+  const int C = x.size(1);
+  TORCH_CHECK(coeffs.is_cuda() && coeffs.is_contiguous() &&
+              coeffs.scalar_type() == at::kFloat && coeffs.dim() == 2 &&
+              coeffs.size(0) == 3 && coeffs.size(1) == C,
+              "coeffs must be fp32 [3][C]");
+  auto dx = at::empty_like(x);
+  auto dres = need_dres ? at::empty_like(x) : at::empty({0}, x.options());
+  launch_bn_bwd_vec(dy, x, y, dx, dres, coeffs.data_ptr<float>(), relu,
+                    training, need_dres);
+  return {dx, dres};
+}
+
 std::vector<at::Tensor> bn_bwd(at::Tensor dy, at::Tensor x, at::Tensor weight,
                                at::Tensor mean, at::Tensor invstd,
                                at::Tensor sum_dy, at::Tensor sum_dy_xhat,
@@ -1283,35 +1650,23 @@ std::vector<at::Tensor> bn_bwd(at::Tensor dy, at::Tensor x, at::Tensor weight,
   auto dres = need_dres ? at::empty_like(x) : at::empty({0}, x.options());
   auto wf = weight.to(at::kFloat).contiguous();
   const int blocks = (int)std::min((total + 1023) / 1024, (long)4096);
+  if (bn_vec_ok(x)) {
+    auto coeffs = at::empty({3, C}, x.options().dtype(at::kFloat));
+    float* A = coeffs.data_ptr<float>();
+    float* B = A + C;
+    float* D = B + C;
+    hipLaunchKernelGGL(bn_bwd_coeffs_kernel, dim3((C + 255) / 256),
+                       dim3(256), 0, cur_stream(), wf.data_ptr<float>(),
+                       mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                       sum_dy.data_ptr<float>(),
+                       sum_dy_xhat.data_ptr<float>(),
+                       (float)(1.0 / count), training, A, B, D, C);
+    launch_bn_bwd_vec(dy, x, y, dx, dres, A, relu, training, need_dres);
+    return {dx, dres};
+  }
   AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::Half, at::ScalarType::BFloat16,
       x.scalar_type(), "bn_bwd", [&] {
-    const bool vec_ok = (total % 8 == 0) &&
-        (clast ? (C % 8 == 0) : (S % 8 == 0));
     auto launch = [&](auto relu_c, auto train_c, auto dres_c, auto cl_c) {
-      if (vec_ok && sizeof(scalar_t) == 2) {
-        auto coeffs = at::empty({3, C}, x.options().dtype(at::kFloat));
-        float* A = coeffs.data_ptr<float>();
-        float* B = A + C;
-        float* D = B + C;
-        hipLaunchKernelGGL(bn_bwd_coeffs_kernel, dim3((C + 255) / 256),
-                           dim3(256), 0, cur_stream(), wf.data_ptr<float>(),
-                           mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                           sum_dy.data_ptr<float>(),
-                           sum_dy_xhat.data_ptr<float>(),
-                           (float)(1.0 / count), training, A, B, D, C);
-        const long nvec = total / 8;
-        const int vblocks = (int)std::min((nvec + 255) / 256, (long)2048);
-        hipLaunchKernelGGL((bn_bwd_vec_kernel<scalar_t, decltype(relu_c)::value,
-                                              decltype(train_c)::value,
-                                              decltype(dres_c)::value,
-                                              decltype(cl_c)::value>),
-                           dim3(vblocks), dim3(256), 0, cur_stream(),
-                           dy.data_ptr<scalar_t>(), x.data_ptr<scalar_t>(),
-                           y.data_ptr<scalar_t>(), dx.data_ptr<scalar_t>(),
-                           need_dres ? dres.data_ptr<scalar_t>() : nullptr,
-                           A, B, D, nvec, C, S);
-        return;
-      }
       hipLaunchKernelGGL((bn_bwd_kernel<scalar_t, decltype(relu_c)::value,
                                         decltype(train_c)::value,
                                         decltype(dres_c)::value,
@@ -1625,6 +1980,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_fwd", &bn_fwd, "fused BN(+add)(+relu) forward");
   m.def("bn_bwd_reduce", &bn_bwd_reduce, "BN backward reductions w/ relu mask");
   m.def("bn_bwd", &bn_bwd, "BN backward apply");
+  m.def("bn_v2_ok", &bn_v2_ok, "x takes the NHWC v2 partial/tail path");
+  m.def("bn_stats_partial", &bn_stats_partial,
+        "NHWC v2 {sum,sqsum} partial [split][2C], unreduced");
+  m.def("bn_fwd_tail", &bn_fwd_tail,
+        "partial -> {stats [4][C], mean, invstd} + running stats, one launch");
+  m.def("bn_fwd_apply", &bn_fwd_apply,
+        "fused BN(+add)(+relu) forward from bn_fwd_tail's stats");
+  m.def("bn_bwd_reduce_partial", &bn_bwd_reduce_partial,
+        "NHWC v2 {sum_dy,sum_dy_xhat} partial [split][2C], unreduced");
+  m.def("bn_bwd_tail", &bn_bwd_tail,
+        "partial -> {dbeta, dgamma, coeffs [3][C]}, one launch");
+  m.def("bn_bwd_tail_dup", &bn_bwd_tail_dup,
+        "partial -> {dbeta, dgamma, packed [2C]} for the SyncBN all_reduce");
+  m.def("bn_bwd_apply", &bn_bwd_apply,
+        "BN backward apply from bn_bwd_tail's coeffs");
   m.def("xent_fwd", &xent_fwd, "fused softmax cross-entropy forward");
   m.def("xent_bwd", &xent_bwd, "fused softmax cross-entropy backward");
   m.def("multi_tensor_sgd", &multi_tensor_sgd, "fused multi-tensor SGD step");

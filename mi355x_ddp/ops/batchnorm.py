@@ -93,6 +93,16 @@ class _FusedBNFunction(torch.autograd.Function):
             residual = residual.contiguous(memory_format=fmt)
         ctx.fmt = fmt
         N, C, H, W = x.shape
+        # tail path (every ResNet BN under bf16/fp16 NHWC with fp32 affine
+        # params): the per-channel bookkeeping between the two big kernels of
+        # a pass is ONE tail launch. Forward: stats partials -> bn_fwd_tail
+        # (reduce + mean/invstd + running stats + scale/shift fold) -> apply.
+        # Backward: reduce partials -> bn_bwd_tail (reduce + dgamma/dbeta +
+        # A/B/D fold) -> apply. 3 launches per pass where the general chain
+        # below takes 5, and no D2D copies for dgamma/dbeta.
+        tail = _backend.native_enabled(x) and weight.dtype == torch.float32 \
+            and bias.dtype == torch.float32 and _backend.C().bn_v2_ok(x)
+        y = None
         if training:
             # count is computed arithmetically (equal per-rank batches are
             # guaranteed by drop_last sharding) — no .item() host sync per BN
@@ -102,7 +112,21 @@ class _FusedBNFunction(torch.autograd.Function):
                 and dist.get_world_size(process_group) > 1
             if synced:
                 cnt *= dist.get_world_size(process_group)
-            if _backend.native_enabled(x):
+            if tail:
+                C_ = _backend.C()
+                if synced:
+                    # the all_reduce wants the reduced [2C]; the tail then
+                    # takes it as a single partial row
+                    part = C_.bn_stats_packed(x)
+                    dist.all_reduce(part, op=dist.ReduceOp.SUM,
+                                    group=process_group)
+                else:
+                    part = C_.bn_stats_partial(x)
+                stats, mean, invstd = C_.bn_fwd_tail(
+                    part, weight, bias, cnt, momentum, eps, running_mean,
+                    running_var)
+                y = C_.bn_fwd_apply(x, stats, relu, residual)
+            elif _backend.native_enabled(x):
                 # packed {sum,sqsum} [2C]: one stats kernel, one optional RCCL
                 # all_reduce, one finalize launch (mean/invstd + running-stats
                 # update) — replaces the eager mean/var/rsqrt/lerp chain.
@@ -131,13 +155,15 @@ class _FusedBNFunction(torch.autograd.Function):
             mean = running_mean.float()
             invstd = torch.rsqrt(running_var.float() + eps)
             cnt = float(N * H * W)
-        y = _fwd_apply(x, weight, bias, mean, invstd, relu, residual)
+        if y is None:
+            y = _fwd_apply(x, weight, bias, mean, invstd, relu, residual)
         ctx.save_for_backward(x, weight, mean, invstd, y)
         ctx.relu = relu
         ctx.training = training
         ctx.count = cnt
         ctx.process_group = process_group
         ctx.has_residual = residual is not None
+        ctx.tail = tail
         return y
 
     @staticmethod
@@ -149,19 +175,35 @@ class _FusedBNFunction(torch.autograd.Function):
         synced = ctx.training and ctx.process_group is not None \
             and dist.is_initialized() \
             and dist.get_world_size(ctx.process_group) > 1
-        if _backend.native_enabled(x):
-            packed = _backend.C().bn_bwd_reduce_packed(dy, x, mean, invstd, y,
-                                                       ctx.relu)
-        else:
-            s_dy, s_dyx = _bwd_reduce(dy, x, mean, invstd, y, ctx.relu)
-            packed = torch.cat([s_dy, s_dyx])
         # dgamma/dbeta are the LOCAL sums — the DP gradient all-reduce averages
         # them like every other parameter grad. The cross-rank-summed versions
         # are only for dx (whose formula needs the GLOBAL batch statistics).
-        # copy=True: the all_reduce below mutates `packed` in place and these
-        # must keep the LOCAL values
-        dgamma = packed[C:].to(weight.dtype, copy=True)
-        dbeta = packed[:C].to(weight.dtype, copy=True)
+        if ctx.tail:
+            C_ = _backend.C()
+            part = C_.bn_bwd_reduce_partial(dy, x, mean, invstd, y, ctx.relu)
+            if not synced:
+                # dbeta/dgamma are the rows of one fresh [2][C] tensor
+                dbeta, dgamma, coeffs = C_.bn_bwd_tail(
+                    part, weight, mean, invstd, 1.0 / count, ctx.training)
+                dx, dresidual = C_.bn_bwd_apply(
+                    dy, x, y, coeffs, ctx.relu, ctx.training, ctx.has_residual)
+                if not ctx.has_residual:
+                    dresidual = None
+                return (dx, dresidual, dgamma, dbeta) + (None,) * 7
+            # the tail writes the sums twice: local rows for the grads, and
+            # `packed` for the all_reduce to overwrite with the global sums
+            dbeta, dgamma, packed = C_.bn_bwd_tail_dup(part)
+        else:
+            if _backend.native_enabled(x):
+                packed = _backend.C().bn_bwd_reduce_packed(dy, x, mean, invstd,
+                                                           y, ctx.relu)
+            else:
+                s_dy, s_dyx = _bwd_reduce(dy, x, mean, invstd, y, ctx.relu)
+                packed = torch.cat([s_dy, s_dyx])
+            # copy=True: the all_reduce below mutates `packed` in place and
+            # these must keep the LOCAL values
+            dgamma = packed[C:].to(weight.dtype, copy=True)
+            dbeta = packed[:C].to(weight.dtype, copy=True)
         if synced:
             dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=ctx.process_group)
         sum_dy, sum_dy_xhat = packed[:C], packed[C:]
