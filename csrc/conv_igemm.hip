@@ -11,7 +11,7 @@
 //          (wT = weight rotated 180° and transposed to [C][R][S][K], built
 //           host-side — a few KB)
 //   wgrad: dw[Kout][R*S*C]  = dy^T[Kout][N*P*Q]     @ im2col(x)[N*P*Q][R*S*C]
-//          (split-K over N*P*Q chunks, fp32 atomics into a dw accumulator)
+//          (split-K over N*P*Q chunks, private fp32 partial slabs + reduce)
 //
 // FAST path: when the contiguous channel count is a multiple of BK(=64) a
 // BK-sized reduction chunk lies inside ONE (r,s) filter tap with a contiguous
@@ -357,8 +357,10 @@ void conv_igemm_kernel(const __bf16* __restrict__ Ag,
 // 64x64 output tile per block, 2x2 waves of 32x32; split-K over NPQ chunks.
 // Each grid.z slice accumulates ITS chunks in registers and stores a private
 // fp32 partial slab (no atomics — round 1's fp32 atomicAdd contention was the
-// main wgrad cost at small tm*tn); wgrad_reduce_kernel sums the slabs and
-// emits the bf16 channels_last weight grad in one pass. DIRECT (splits==1,
+// main wgrad cost at small tm*tn); a reduce kernel sums the slabs and
+// emits the bf16 channels_last weight grad in one pass. Slices beyond one
+// resident set of blocks (CUs x blocks per CU) add slab traffic, not
+// parallelism: splits < 0 asks for exactly that set. DIRECT (splits==1,
 // no channel padding): the slab and reduce collapse away — the kernel writes
 // bf16 dw itself. Both LDS tiles are written transposed (reduction index
 // contiguous per row) so MFMA fragment reads are 16-byte ds_read_b128.
@@ -367,6 +369,28 @@ void conv_igemm_kernel(const __bf16* __restrict__ Ag,
 // ATOMIC: all grid.z slices atomicAdd into ONE fp32 slab (round 1's scheme)
 // instead of private slabs — wins on small dw where the slab+reduce pass
 // costs more than the contention; kept as autotune variant wtile=4.
+//
+// Partial-slab layout. The ATOMIC slab is row-major [m][n] and goes through
+// wgrad_reduce_kernel. Every other split-K launch (v1 with the stem, v2,
+// LIN) stores FRAGMENT-ORDER slabs
+//   part[z][tile][f][tid] of f32x4,  tile = blockIdx.y * gridDim.x + blockIdx.x,
+// where f = mi * 4 + ni walks the block's accumulator array and tid is the
+// thread: the block dumps its registers as they are, one 16-byte store per
+// lane per fragment, a wave covering 1 KiB contiguous (row-major cost one
+// dword store per accumulator ELEMENT, four 64-byte pieces per wave
+// instruction). A tile's region is TM*TN floats, edge tiles included: their
+// out-of-range rows/columns are stored as accumulated and dropped by
+// wgrad_reduce_frag_kernel, which undoes the permutation.
+template <int NF>
+__device__ __forceinline__ void store_frag_slab(float* __restrict__ dwp,
+                                                const f32x4* acc, int tid) {
+  const long ntiles = (long)gridDim.x * gridDim.y;
+  const long tile = (long)blockIdx.y * gridDim.x + blockIdx.x;
+  f32x4* dst = (f32x4*)dwp + (blockIdx.z * ntiles + tile) * (NF * 256) + tid;
+  #pragma unroll
+  for (int f = 0; f < NF; ++f) dst[f * 256] = acc[f];
+}
+
 template <bool FAST, bool PADC = false, bool DIRECT = false,
           bool ATOMIC = false>
 __global__ __launch_bounds__(256)
@@ -507,6 +531,10 @@ void conv_wgrad_kernel(const __bf16* __restrict__ dy,
     __syncthreads();
   }
 
+  if constexpr (!DIRECT && !ATOMIC) {
+    store_frag_slab<8>(dwp, &acc[0][0], tid);
+    return;
+  }
   const int dm = (lane >> 4) * 4;
   const int dn = lane & 15;
   float* slab = DIRECT ? nullptr
@@ -754,9 +782,12 @@ void conv_wgrad_v2_kernel(const __bf16* __restrict__ dy,
     }
   }
 
+  if constexpr (!DIRECT) {
+    store_frag_slab<16>(dwp, &acc[0][0], tid);
+    return;
+  }
   const int dm = (lane >> 4) * 4;
   const int dn = lane & 15;
-  float* slab = DIRECT ? nullptr : dwp + (long)blockIdx.z * d.M * d.N;
   #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
     #pragma unroll
@@ -767,8 +798,7 @@ void conv_wgrad_v2_kernel(const __bf16* __restrict__ dy,
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + wm + mi * 16 + dm + r;
         if (m >= d.M) continue;
-        if (DIRECT) dwb[(long)m * d.N + n] = (__bf16)acc[mi][ni][r];
-        else slab[(long)m * d.N + n] = acc[mi][ni][r];
+        dwb[(long)m * d.N + n] = (__bf16)acc[mi][ni][r];
       }
     }
 }
@@ -916,9 +946,12 @@ void conv_wgrad_lin_kernel(const __bf16* __restrict__ dy,
     }
   }
 
+  if constexpr (!DIRECT) {
+    store_frag_slab<16>(dwp, &acc[0][0], tid);
+    return;
+  }
   const int dm = (lane >> 4) * 4;
   const int dn = lane & 15;
-  float* slab = DIRECT ? nullptr : dwp + (long)blockIdx.z * d.M * d.N;
   #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
     #pragma unroll
@@ -929,8 +962,7 @@ void conv_wgrad_lin_kernel(const __bf16* __restrict__ dy,
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + wm + mi * 16 + dm + r;
         if (m >= d.M) continue;
-        if (DIRECT) dwb[(long)m * d.N + n] = (__bf16)acc[mi][ni][r];
-        else slab[(long)m * d.N + n] = acc[mi][ni][r];
+        dwb[(long)m * d.N + n] = (__bf16)acc[mi][ni][r];
       }
     }
 }
@@ -957,6 +989,100 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ part,
     for (int z = 0; z < splits; ++z) s += part[(long)z * MN + o];
     dw[m * Nout + nout] = (__bf16)s;
   }
+}
+
+// Reduce for fragment-order slabs (layout: see store_frag_slab). A "slot" is
+// one f32x4 of one thread of one tile; slot e of every z slice sits at
+// part[z * nslots + e], so the sum over z is a stride-nslots walk of 16-byte
+// loads, coalesced across the threads of a slot group whatever the tile shape.
+// A thread sums V floats of a slot (4: the whole slot, 16-byte loads; 1: a
+// quarter, for small dw that must keep ZW == 1), and a block is ZW z-groups
+// of 256/ZW consecutive units: small dw takes a larger ZW, or V == 1, so the
+// grid still covers the chip.
+// Summation order (fixed, so results are bit-reproducible for a given
+// (wtile, splits)): z-group g adds z = g, g+ZW, g+2*ZW, ... in increasing
+// order into one fp32 accumulator (loads double-buffered eight at a time,
+// adds in sequence); then the group partials are added in the order g = 0,
+// 1, .., ZW-1 through LDS. ZW == 1 is the plain z = 0, 1, 2, ... order of
+// wgrad_reduce_kernel: the default path (splits == 0) uses it, so that its
+// gradients keep the bits they always had.
+// Un-permute: slot -> (tile, f, tid) -> rows m..m+3 and column n exactly as
+// the MFMA accumulator maps them (NF fragments = NF/4 x 4 of 16x16 per wave,
+// WGN waves along n); rows/columns past M/N (edge tiles) are dropped, and
+// the stem's padded columns are mapped as in wgrad_reduce_kernel.
+template <int V>
+__device__ __forceinline__ f32x4 ld_frag(const float* p) {
+  if constexpr (V == 4) return *(const f32x4*)p;
+  else return f32x4{*p, 0.f, 0.f, 0.f};
+}
+
+template <int ZW, int V>
+__global__ __launch_bounds__(256)
+void wgrad_reduce_frag_kernel(const float* __restrict__ part,
+                              __bf16* __restrict__ dw, int M, int N, int tn,
+                              long nslots, int splits, int NF, int WGN,
+                              int Nout, int Cpad, int Cout) {
+  static_assert(V == 4 || (V == 1 && ZW == 1), "V == 1 is sequential only");
+  constexpr int SPB = 256 / ZW;  // units per block; nslots % 256 == 0
+  constexpr int U = 8;           // loads per batch
+  __shared__ f32x4 red[ZW > 1 ? 256 : 1];
+  const int tid = threadIdx.x;
+  const int zg = tid / SPB;
+  const long u = (long)blockIdx.x * SPB + (tid % SPB);   // unit of V floats
+  const float* p = part + u * V;
+  const long zstride = nslots * 4;
+  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  f32x4 cur[U], nxt[U];
+  // a slice past the end contributes +0.f, which leaves s as it is
+  auto load = [&](f32x4 (&v)[U], int z0) {
+    #pragma unroll
+    for (int i = 0; i < U; ++i) {
+      const int z = z0 + i * ZW;
+      v[i] = z < splits ? ld_frag<V>(p + (long)z * zstride)
+                        : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  };
+  load(cur, zg);
+  for (int z0 = zg; z0 < splits; z0 += U * ZW) {
+    const int zn = z0 + U * ZW;
+    if (zn < splits) load(nxt, zn);   // in flight while cur is added
+    #pragma unroll
+    for (int i = 0; i < U; ++i) s += cur[i];
+    if (zn < splits) {
+      #pragma unroll
+      for (int i = 0; i < U; ++i) cur[i] = nxt[i];
+    }
+  }
+  if (ZW > 1) {
+    red[tid] = s;
+    __syncthreads();
+    if (zg != 0) return;
+    #pragma unroll
+    for (int g = 1; g < ZW; ++g) s += red[g * SPB + tid];
+  }
+  const long e = u * V >> 2;               // slot
+  const int r0 = (int)(u * V & 3);         // first of this thread's V rows
+  const int per = NF * 256;
+  const int tile = (int)(e / per);
+  const int w = (int)(e - (long)tile * per);
+  const int f = w >> 8, t = w & 255;
+  const int wave = t >> 6, lane = t & 63;
+  const int wtm = (NF >> 2) * 16;           // wave tile rows
+  const int by = tile / tn, bx = tile - by * tn;
+  const int m = by * (4 / WGN) * wtm + (wave / WGN) * wtm + (f >> 2) * 16 +
+                (lane >> 4) * 4;
+  const int n = bx * WGN * 64 + (wave % WGN) * 64 + (f & 3) * 16 + (lane & 15);
+  if (n >= N) return;
+  int nout = n;
+  if (Cpad != Cout) {  // stem: drop the pad channel and taps >= R*S
+    const int tap = n / Cpad, c = n - tap * Cpad;
+    if (c >= Cout || tap * Cout >= Nout) return;
+    nout = tap * Cout + c;
+  }
+  #pragma unroll
+  for (int r = 0; r < V; ++r)
+    if (m + r0 + r < M)
+      dw[(long)(m + r0 + r) * Nout + nout] = (__bf16)s[r];
 }
 
 // wT[c][i][j][k] = w[k][R-1-i][S-1-j][c] — the 180°-rotated transposed filter
@@ -1186,10 +1312,24 @@ at::Tensor conv_dgrad_igemm(at::Tensor dy, at::Tensor wT, long H, long W,
 }
 
 // dw bf16 (K,C,R,S) channels_last <- dy, x. Two-stage split-K: private fp32
-// partial slabs per grid.z slice + one reduce pass (no atomics); splits==1
-// non-stem collapses to a DIRECT bf16 store. `splits`: 0 = heuristic.
+// partial slabs per grid.z slice (fragment order, see store_frag_slab) + one
+// reduce pass (no atomics); splits==1 non-stem collapses to a DIRECT bf16
+// store. `splits`: 0 = default (~1024 blocks, plain z order: the bits this
+// path has always produced), < 0 = one resident set of blocks, > 0 = as given.
 // `wtile`: 0 = shape heuristic, 1 = v1 64x128, 2 = v2 128x128, 3 = v2 256x64
 // (the autotune cache measures and pins these per shape).
+namespace {
+// Blocks per CU the split heuristic aims at, per tile family (resolved wtile).
+// v2 / LIN are __launch_bounds__(256, 2): two blocks are resident per CU, and
+// the split sweep has its optimum there (1x: +40-70 %; 3x, a partial second
+// round: +15-35 %; 4x: up to +11 %). v1 (27 KB LDS, ~60 VGPRs) fits five;
+// its sweep is flat from 3x to 5x with the minimum at 4x
+// (profiles/r4_wgrad_split_sweep.txt).
+inline int wgrad_blocks_per_cu(int tile) {
+  return (tile == 1 || tile == 4) ? 4 : 2;
+}
+}  // namespace
+
 at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
                             long stride, long pad, long splits_arg,
                             long wtile) {
@@ -1247,13 +1387,23 @@ at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
   // wide-stage v2 (wtile 8/9) strides 128-row stages: a z-slice beyond the
   // stage count would leave its partial slab unwritten
   const int nzmax = (tile == 8 || tile == 9) ? (nchunks + 1) / 2 : nchunks;
-  // heuristic: ~1024 blocks fills the chip, but keep >=8 chunks per block
-  // (fewer and the per-block fill/drain + slab traffic dominates — measured
-  // on the CIFAR shapes, where over-splitting cost 2-4x)
+  // splits < 0, residency-sized: one resident set of blocks (CUs x blocks
+  // per CU, see wgrad_blocks_per_cu) — every slice beyond that queues behind
+  // the first round and only adds a TM*TN fp32 slab to write and re-read.
+  // splits == 0, the default: the ~1024 blocks this path has always used,
+  // summed in plain z order. Slice count and order decide the last bit of a
+  // bf16 gradient, and a training run amplifies that bit (25 flagship steps
+  // turn it into 18 % of the parameter norm), so the default keeps both and
+  // with them every bit of a --reproducible run; the autotuner measures the
+  // residency-sized count as one of its candidates. Either way keep >=8
+  // chunks per block (fewer and the per-block fill/drain + slab traffic
+  // dominates — measured on the CIFAR shapes, where over-splitting cost 2-4x)
+  const int cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  const int target = splits_arg < 0 ? cus * wgrad_blocks_per_cu(tile) : 1024;
   int splits = (splits_arg > 0) ? (int)splits_arg
-                                : std::min(1024 / (tm * tn), nchunks / 8);
-  // bound the partial-slab workspace to ~96 MB
-  const long max_ws = 96L * 1024 * 1024 / ((long)d.M * d.N * 4);
+                                : std::min(target / (tm * tn), nchunks / 8);
+  // bound the partial-slab workspace to ~96 MB (slabs hold whole tiles)
+  const long max_ws = 96L * 1024 * 1024 / ((long)tm * tn * TM * TN * 4);
   splits = std::max(1, (int)std::min({(long)splits, (long)nzmax,
                                       std::max(max_ws, 1L), 1024L}));
   const dim3 grid(tn, tm, splits);
@@ -1274,10 +1424,12 @@ at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
   }
 
   const bool atomic = (tile == 4);
+  const bool rowmajor = atomic;           // else fragment-order slabs
   const long MN = (long)d.M * d.N;
+  const long slab = rowmajor ? MN : (long)tm * tn * TM * TN;
   auto part = atomic
       ? at::zeros({MN}, x.options().dtype(at::kFloat))
-      : at::empty({(long)splits * MN}, x.options().dtype(at::kFloat));
+      : at::empty({(long)splits * slab}, x.options().dtype(at::kFloat));
   auto* kern =
       tile == 9 ? conv_wgrad_v2_kernel<4, 1, false, 2>
       : tile == 8 ? conv_wgrad_v2_kernel<2, 2, false, 2>
@@ -1293,6 +1445,29 @@ at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
                      : conv_wgrad_kernel<false, false, false>);
   hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, bf16_ptr(dy), xp,
                      part.data_ptr<float>(), nullptr, d);
+  if (!rowmajor) {
+    const int NF = TM * TN / 1024;         // f32x4 fragments per thread
+    const long nslots = slab / 4;
+    // smallest z-group count that gives the reduce two blocks per CU, while
+    // every group still has four slices to keep in flight; the default path
+    // keeps plain z order and narrows the per-thread unit instead
+    const bool seq = (splits_arg == 0);
+    int zw = 1;
+    while (!seq && zw < 16 && nslots * zw / 256 < 2L * cus && zw * 8 <= splits)
+      zw *= 2;
+    const int v = (seq && nslots / 256 < 2L * cus) ? 1 : 4;
+    auto* red = v == 1 ? wgrad_reduce_frag_kernel<1, 1>
+              : zw == 1 ? wgrad_reduce_frag_kernel<1, 4>
+              : zw == 2 ? wgrad_reduce_frag_kernel<2, 4>
+              : zw == 4 ? wgrad_reduce_frag_kernel<4, 4>
+              : zw == 8 ? wgrad_reduce_frag_kernel<8, 4>
+                        : wgrad_reduce_frag_kernel<16, 4>;
+    hipLaunchKernelGGL(red, dim3((unsigned)(nslots * zw * (4 / v) / 256)),
+                       dim3(256), 0, stream, part.data_ptr<float>(),
+                       reinterpret_cast<__bf16*>(dw.data_ptr()), d.M, d.N, tn,
+                       nslots, splits, NF, TN / 64, (int)(R * S * C), Cpad, C);
+    return dw;
+  }
   hipLaunchKernelGGL(wgrad_reduce_kernel,
                      dim3((int)std::min((MN + 255) / 256, (long)4096)),
                      dim3(256), 0, stream, part.data_ptr<float>(),

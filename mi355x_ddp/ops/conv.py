@@ -193,17 +193,20 @@ class _ConvIGEMM(torch.autograd.Function):
             # split-K factor for the winning native tile
             kt = ("wgrad_tile", dy.shape, x.shape, R, ctx.stride, ctx.padding)
             tile = _tuned_choice(
-                kt, ((0, 0), (1, 0), (2, 0), (3, 0), (4, 0), (5, 0), (6, 0),
-                     MIOPEN),
+                kt, ((0, 0), (1, -1), (2, -1), (3, -1), (4, 0), (5, -1),
+                     (6, -1), MIOPEN),
                 run_dw, default=(0, 0))
             if tile == MIOPEN:
                 choice = MIOPEN
             else:
                 ks = ("wgrad_splits", dy.shape, x.shape, R, ctx.stride,
                       ctx.padding, tile[0])
+                # 0 = the kernel's default (~1024 blocks, the bit-stable
+                # count), -1 = one resident set of blocks (3..200 slices on
+                # the ResNet shapes); the explicit counts bracket both
                 choice = _tuned_choice(
-                    ks, tuple((tile[0], s) for s in (0, 1, 32, 128)), run_dw,
-                    default=tile)
+                    ks, tuple((tile[0], s) for s in (0, -1, 1, 32, 128)),
+                    run_dw, default=tile)
             dw = run_dw(choice)
         return dx, dw, None, None
 
