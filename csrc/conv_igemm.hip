@@ -381,6 +381,16 @@ void conv_igemm_kernel(const __bf16* __restrict__ Ag,
 // instruction). A tile's region is TM*TN floats, edge tiles included: their
 // out-of-range rows/columns are stored as accumulated and dropped by
 // wgrad_reduce_frag_kernel, which undoes the permutation.
+// Every dw element leaves through here. The value is rounded to bf16 either
+// way; f32 stores that rounded value widened (exact), for an fp32 parameter
+// whose gradient would otherwise be widened by a separate cast kernel.
+__device__ __forceinline__ void store_dw(void* __restrict__ dw, bool f32,
+                                         long idx, float v) {
+  const __bf16 b = (__bf16)v;
+  if (f32) ((float*)dw)[idx] = (float)b;
+  else ((__bf16*)dw)[idx] = b;
+}
+
 template <int NF>
 __device__ __forceinline__ void store_frag_slab(float* __restrict__ dwp,
                                                 const f32x4* acc, int tid) {
@@ -397,7 +407,7 @@ __global__ __launch_bounds__(256)
 void conv_wgrad_kernel(const __bf16* __restrict__ dy,
                        const __bf16* __restrict__ x,
                        float* __restrict__ dwp,
-                       __bf16* __restrict__ dwb, ConvDims d) {
+                       void* __restrict__ dwb, ConvDims d, bool f32) {
   // d: M = Kout, N = R*S*C, K = Nb*P*Q; OH/OW = P,Q; GH/GW/GC = H,W,C
   // 64(Kout) x 128(rsc) tile: each loaded byte feeds twice the MFMA work of
   // the 64x64 tile. FAST needs C % 64 == 0 so every 32-wide rsc sub-chunk
@@ -549,7 +559,7 @@ void conv_wgrad_kernel(const __bf16* __restrict__ dy,
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + wm + mi * 16 + dm + r;
         if (m >= d.M) continue;
-        if (DIRECT) dwb[(long)m * d.N + n] = (__bf16)acc[mi][ni][r];
+        if (DIRECT) store_dw(dwb, f32, (long)m * d.N + n, acc[mi][ni][r]);
         else if (ATOMIC) atomicAdd(&slab[(long)m * d.N + n], acc[mi][ni][r]);
         else slab[(long)m * d.N + n] = acc[mi][ni][r];
       }
@@ -591,7 +601,7 @@ __global__ __launch_bounds__(256, 2)
 void conv_wgrad_v2_kernel(const __bf16* __restrict__ dy,
                           const __bf16* __restrict__ x,
                           float* __restrict__ dwp,
-                          __bf16* __restrict__ dwb, ConvDims d) {
+                          void* __restrict__ dwb, ConvDims d, bool f32) {
   constexpr int TM = WGM * 64;          // kout tile
   constexpr int TN = WGN * 64;          // rsc tile
   constexpr int TA = TM / 64;
@@ -798,7 +808,7 @@ void conv_wgrad_v2_kernel(const __bf16* __restrict__ dy,
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + wm + mi * 16 + dm + r;
         if (m >= d.M) continue;
-        dwb[(long)m * d.N + n] = (__bf16)acc[mi][ni][r];
+        store_dw(dwb, f32, (long)m * d.N + n, acc[mi][ni][r]);
       }
     }
 }
@@ -817,7 +827,7 @@ __global__ __launch_bounds__(256, 2)  // 2 waves/SIMD: the double buffer
 void conv_wgrad_lin_kernel(const __bf16* __restrict__ dy,
                            const __bf16* __restrict__ x,
                            float* __restrict__ dwp,
-                           __bf16* __restrict__ dwb, ConvDims d) {
+                           void* __restrict__ dwb, ConvDims d, bool f32) {
   constexpr int TM = WGM * 64;
   constexpr int TN = WGN * 64;
   constexpr int TA = TM / 64;
@@ -962,7 +972,7 @@ void conv_wgrad_lin_kernel(const __bf16* __restrict__ dy,
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + wm + mi * 16 + dm + r;
         if (m >= d.M) continue;
-        dwb[(long)m * d.N + n] = (__bf16)acc[mi][ni][r];
+        store_dw(dwb, f32, (long)m * d.N + n, acc[mi][ni][r]);
       }
     }
 }
@@ -972,7 +982,7 @@ void conv_wgrad_lin_kernel(const __bf16* __restrict__ dy,
 // Cpad==Cout -> identity column map; the stem maps Cpad=4 -> Cout=3 and drops
 // the zero-pad channel and any tap >= R*S.
 __global__ void wgrad_reduce_kernel(const float* __restrict__ part,
-                                    __bf16* __restrict__ dw,
+                                    void* __restrict__ dw, bool f32,
                                     long MN, int N, int Nout, int splits,
                                     int Cpad, int Cout) {
   for (long o = (long)blockIdx.x * blockDim.x + threadIdx.x; o < MN;
@@ -987,7 +997,7 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ part,
     }
     float s = 0.f;
     for (int z = 0; z < splits; ++z) s += part[(long)z * MN + o];
-    dw[m * Nout + nout] = (__bf16)s;
+    store_dw(dw, f32, m * Nout + nout, s);
   }
 }
 
@@ -1019,7 +1029,8 @@ __device__ __forceinline__ f32x4 ld_frag(const float* p) {
 template <int ZW, int V>
 __global__ __launch_bounds__(256)
 void wgrad_reduce_frag_kernel(const float* __restrict__ part,
-                              __bf16* __restrict__ dw, int M, int N, int tn,
+                              void* __restrict__ dw, bool f32, int M, int N,
+                              int tn,
                               long nslots, int splits, int NF, int WGN,
                               int Nout, int Cpad, int Cout) {
   static_assert(V == 4 || (V == 1 && ZW == 1), "V == 1 is sequential only");
@@ -1082,7 +1093,7 @@ void wgrad_reduce_frag_kernel(const float* __restrict__ part,
   #pragma unroll
   for (int r = 0; r < V; ++r)
     if (m + r0 + r < M)
-      dw[(long)(m + r0 + r) * Nout + nout] = (__bf16)s[r];
+      store_dw(dw, f32, (long)(m + r0 + r) * Nout + nout, s[r]);
 }
 
 // wT[c][i][j][k] = w[k][R-1-i][S-1-j][c] — the 180°-rotated transposed filter
@@ -1100,6 +1111,126 @@ __global__ void build_wT_kernel(const __bf16* __restrict__ w,
     const int i = (int)(t % R);
     const int c = (int)(t / R);
     wT[o] = w[(((long)k * R + (R - 1 - i)) * S + (S - 1 - j)) * C + c];
+  }
+}
+
+// The same rotation for up to 32 filters in one launch, through an LDS tile
+// transpose: a block takes one filter tap of one tensor, 64 k x 64 c. It
+// reads 64 rows of 64 consecutive c (128 B of bf16 each) and writes 64 rows
+// of 64 consecutive k (128 B each), where build_wT_kernel reads 2 bytes at
+// stride R*S*C per lane. IT = float additionally rounds to bf16 and, where
+// w16 is given, stores the rounded copy at the source index: cast + rotate of
+// an fp32 weight in one pass (conv_prep_weight). Rows move as 16-byte units
+// when the row length is a multiple of 8 and the base is 16-byte aligned, and
+// element by element otherwise (ragged C such as the 3-channel stem); either
+// way consecutive lanes touch consecutive addresses, and K or C past the last
+// full tile are predicated off.
+constexpr int WT_MAX_TENSORS = 32;
+
+struct WTList {
+  const void* w[WT_MAX_TENSORS];   // [K][R*S][C], IT
+  __bf16* w16[WT_MAX_TENSORS];     // [K][R*S][C] bf16 copy of w, or null
+  __bf16* wT[WT_MAX_TENSORS];      // [C][R*S][K]
+  int K[WT_MAX_TENSORS], C[WT_MAX_TENSORS], RS[WT_MAX_TENSORS];
+  int nblocks[WT_MAX_TENSORS];     // RS * ceil(K/64) * ceil(C/64)
+  int ntensors;
+};
+
+__device__ __forceinline__ unsigned short wt_bits(float v) {
+  return __builtin_bit_cast(unsigned short, (__bf16)v);
+}
+__device__ __forceinline__ unsigned short wt_bits(__bf16 v) {
+  return __builtin_bit_cast(unsigned short, v);
+}
+
+template <typename IT>
+__global__ __launch_bounds__(256)
+void multi_build_wT_kernel(WTList tl) {
+  // [k][c]; 33-dword rows keep the column reads of the store phase off the
+  // same LDS bank
+  __shared__ unsigned short tile[64][66];
+  int b = blockIdx.x;
+  int t = 0;
+  for (; t < tl.ntensors; ++t) {
+    if (b < tl.nblocks[t]) break;
+    b -= tl.nblocks[t];
+  }
+  if (t >= tl.ntensors) return;
+  const int K = tl.K[t], C = tl.C[t], RS = tl.RS[t];
+  const int tc = (C + 63) / 64;
+  const int c0 = (b % tc) * 64;
+  const int tap = (b / tc) % RS;
+  const int k0 = (b / tc / RS) * 64;
+  const IT* __restrict__ w = (const IT*)tl.w[t];
+  unsigned short* __restrict__ w16 = (unsigned short*)tl.w16[t];
+  unsigned short* __restrict__ wT = (unsigned short*)tl.wT[t];
+  const int tid = threadIdx.x;
+
+  const bool vec_in = C % 8 == 0 && ((size_t)w & 15) == 0 &&
+                      ((size_t)w16 & 15) == 0;
+  if (vec_in) {
+    const int lc = (tid & 7) * 8;
+    #pragma unroll
+    for (int ps = 0; ps < 2; ++ps) {
+      const int kk = (tid >> 3) + 32 * ps;
+      const int k = k0 + kk, c = c0 + lc;
+      if (k >= K || c >= C) continue;
+      const long idx = ((long)k * RS + tap) * C + c;
+      uint4 v;
+      if constexpr (sizeof(IT) == 4) {
+        const float4 a = *(const float4*)(w + idx);
+        const float4 bb = *(const float4*)(w + idx + 4);
+        v.x = wt_bits(a.x) | ((unsigned)wt_bits(a.y) << 16);
+        v.y = wt_bits(a.z) | ((unsigned)wt_bits(a.w) << 16);
+        v.z = wt_bits(bb.x) | ((unsigned)wt_bits(bb.y) << 16);
+        v.w = wt_bits(bb.z) | ((unsigned)wt_bits(bb.w) << 16);
+        if (w16 != nullptr) *(uint4*)(w16 + idx) = v;
+      } else {
+        v = *(const uint4*)(w + idx);
+      }
+      unsigned* dst = (unsigned*)&tile[kk][lc];   // 4-byte aligned only
+      dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+    }
+  } else {
+    #pragma unroll 4
+    for (int e = 0; e < 16; ++e) {
+      const int i = tid + 256 * e;
+      const int kk = i >> 6, cc = i & 63;
+      const int k = k0 + kk, c = c0 + cc;
+      if (k >= K || c >= C) continue;
+      const long idx = ((long)k * RS + tap) * C + c;
+      const unsigned short bits = wt_bits(w[idx]);
+      if (sizeof(IT) == 4 && w16 != nullptr) w16[idx] = bits;
+      tile[kk][cc] = bits;
+    }
+  }
+  __syncthreads();
+
+  const int tapT = RS - 1 - tap;   // (R-1-i, S-1-j) of tap (i, j)
+  const bool vec_out = K % 8 == 0 && ((size_t)wT & 15) == 0;
+  if (vec_out) {
+    const int lk = (tid & 7) * 8;
+    #pragma unroll
+    for (int ps = 0; ps < 2; ++ps) {
+      const int cc = (tid >> 3) + 32 * ps;
+      const int k = k0 + lk, c = c0 + cc;
+      if (k >= K || c >= C) continue;
+      uint4 v;
+      v.x = tile[lk + 0][cc] | ((unsigned)tile[lk + 1][cc] << 16);
+      v.y = tile[lk + 2][cc] | ((unsigned)tile[lk + 3][cc] << 16);
+      v.z = tile[lk + 4][cc] | ((unsigned)tile[lk + 5][cc] << 16);
+      v.w = tile[lk + 6][cc] | ((unsigned)tile[lk + 7][cc] << 16);
+      *(uint4*)(wT + ((long)c * RS + tapT) * K + k) = v;
+    }
+  } else {
+    #pragma unroll 4
+    for (int e = 0; e < 16; ++e) {
+      const int i = tid + 256 * e;
+      const int cc = i >> 6, kk = i & 63;
+      const int k = k0 + kk, c = c0 + cc;
+      if (k >= K || c >= C) continue;
+      wT[((long)c * RS + tapT) * K + k] = tile[kk][cc];
+    }
   }
 }
 
@@ -1173,6 +1304,67 @@ at::Tensor conv_build_wT(at::Tensor w) {
                      conv_stream(), bf16_ptr(w),
                      reinterpret_cast<__bf16*>(wT.data_ptr()), K, R, S, C);
   return wT;
+}
+
+namespace {
+// One WTList entry: src (K,C,R,S) channels_last -> wT (C,R,S,K) contiguous,
+// with an optional bf16 copy of an fp32 src.
+int wt_fill(WTList& tl, int t, const at::Tensor& src, const at::Tensor* w16,
+            const at::Tensor& wT) {
+  TORCH_CHECK(src.is_cuda() && src.dim() == 4 &&
+              src.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "build_wT: filter must be a 4-D channels_last HIP tensor");
+  const long K = src.size(0), C = src.size(1), R = src.size(2), S = src.size(3);
+  TORCH_CHECK(wT.is_cuda() && wT.scalar_type() == at::kBFloat16 &&
+              wT.is_contiguous() && wT.dim() == 4 && wT.size(0) == C &&
+              wT.size(1) == R && wT.size(2) == S && wT.size(3) == K,
+              "build_wT: wT must be a contiguous bf16 (C,R,S,K) tensor");
+  if (w16 != nullptr)
+    TORCH_CHECK(w16->is_cuda() && w16->scalar_type() == at::kBFloat16 &&
+                w16->sizes() == src.sizes() &&
+                w16->is_contiguous(at::MemoryFormat::ChannelsLast),
+                "build_wT: w16 must be bf16 channels_last of the filter's shape");
+  const long nb = R * S * ((K + 63) / 64) * ((C + 63) / 64);
+  TORCH_CHECK(K > 0 && C > 0 && R * S > 0 && nb < (1L << 24),
+              "build_wT: filter too large");
+  tl.w[t] = src.data_ptr();
+  tl.w16[t] = w16 ? reinterpret_cast<__bf16*>(w16->data_ptr()) : nullptr;
+  tl.wT[t] = reinterpret_cast<__bf16*>(wT.data_ptr());
+  tl.K[t] = (int)K; tl.C[t] = (int)C; tl.RS[t] = (int)(R * S);
+  tl.nblocks[t] = (int)nb;
+  return (int)nb;
+}
+}  // namespace
+
+// wT[i] <- rotate(w16[i]) for every filter, one launch per 32 tensors.
+void multi_tensor_build_wT(std::vector<at::Tensor> w16s,
+                           std::vector<at::Tensor> wTs) {
+  TORCH_CHECK(w16s.size() == wTs.size());
+  auto stream = conv_stream();
+  size_t i = 0;
+  while (i < w16s.size()) {
+    WTList tl;
+    int nblocks = 0, t = 0;
+    for (; t < WT_MAX_TENSORS && i < w16s.size(); ++t, ++i) {
+      TORCH_CHECK(w16s[i].scalar_type() == at::kBFloat16,
+                  "multi_tensor_build_wT expects bf16 filters");
+      nblocks += wt_fill(tl, t, w16s[i], nullptr, wTs[i]);
+    }
+    tl.ntensors = t;
+    hipLaunchKernelGGL(multi_build_wT_kernel<__bf16>, dim3(nblocks), dim3(256),
+                       0, stream, tl);
+  }
+}
+
+// w16 <- bf16(w32), wT <- rotate(w16), one launch.
+void conv_prep_weight(at::Tensor w32, at::Tensor w16, at::Tensor wT) {
+  TORCH_CHECK(w32.scalar_type() == at::kFloat,
+              "conv_prep_weight expects an fp32 filter");
+  WTList tl;
+  const int nblocks = wt_fill(tl, 0, w32, &w16, wT);
+  tl.ntensors = 1;
+  hipLaunchKernelGGL(multi_build_wT_kernel<float>, dim3(nblocks), dim3(256), 0,
+                     conv_stream(), tl);
 }
 
 // tile: 0 = size heuristic, 64 or 128 = force that GEMM-M tile (the
@@ -1311,7 +1503,9 @@ at::Tensor conv_dgrad_igemm(at::Tensor dy, at::Tensor wT, long H, long W,
   return dx;
 }
 
-// dw bf16 (K,C,R,S) channels_last <- dy, x. Two-stage split-K: private fp32
+// dw (K,C,R,S) channels_last <- dy, x; bf16, or with out_fp32 the same
+// bf16-rounded values as fp32 (the gradient of an fp32 parameter, with no
+// cast kernel between the epilogue and the optimizer). Two-stage split-K: private fp32
 // partial slabs per grid.z slice (fragment order, see store_frag_slab) + one
 // reduce pass (no atomics); splits==1 non-stem collapses to a DIRECT bf16
 // store. `splits`: 0 = default (~1024 blocks, plain z order: the bits this
@@ -1332,13 +1526,15 @@ inline int wgrad_blocks_per_cu(int tile) {
 
 at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
                             long stride, long pad, long splits_arg,
-                            long wtile) {
+                            long wtile, bool out_fp32) {
   check_nhwc_bf16(dy, "dy"); check_nhwc_bf16(x, "x");
   const int Nb = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int K = dy.size(1), P = dy.size(2), Q = dy.size(3);
   auto stream = conv_stream();
+  // out_fp32: same shape and strides, the bf16-rounded values widened
   auto dw = at::empty({K, C, R, S},
-                      x.options().memory_format(at::MemoryFormat::ChannelsLast));
+                      x.options().memory_format(at::MemoryFormat::ChannelsLast)
+                          .dtype(out_fp32 ? at::kFloat : at::kBFloat16));
 
   const bool stem = (C == 3);
   int Cpad = C, Npad = (int)(R * S * C);
@@ -1419,7 +1615,7 @@ at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
         : (fast ? conv_wgrad_kernel<true, false, true>
                 : conv_wgrad_kernel<false, false, true>);
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, bf16_ptr(dy), xp,
-                       nullptr, reinterpret_cast<__bf16*>(dw.data_ptr()), d);
+                       nullptr, dw.data_ptr(), d, out_fp32);
     return dw;
   }
 
@@ -1444,7 +1640,7 @@ at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
              : (fast ? conv_wgrad_kernel<true, false, false>
                      : conv_wgrad_kernel<false, false, false>);
   hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, bf16_ptr(dy), xp,
-                     part.data_ptr<float>(), nullptr, d);
+                     part.data_ptr<float>(), nullptr, d, out_fp32);
   if (!rowmajor) {
     const int NF = TM * TN / 1024;         // f32x4 fragments per thread
     const long nslots = slab / 4;
@@ -1464,14 +1660,14 @@ at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
                         : wgrad_reduce_frag_kernel<16, 4>;
     hipLaunchKernelGGL(red, dim3((unsigned)(nslots * zw * (4 / v) / 256)),
                        dim3(256), 0, stream, part.data_ptr<float>(),
-                       reinterpret_cast<__bf16*>(dw.data_ptr()), d.M, d.N, tn,
-                       nslots, splits, NF, TN / 64, (int)(R * S * C), Cpad, C);
+                       dw.data_ptr(), out_fp32, d.M, d.N, tn, nslots, splits,
+                       NF, TN / 64, (int)(R * S * C), Cpad, C);
     return dw;
   }
   hipLaunchKernelGGL(wgrad_reduce_kernel,
                      dim3((int)std::min((MN + 255) / 256, (long)4096)),
                      dim3(256), 0, stream, part.data_ptr<float>(),
-                     reinterpret_cast<__bf16*>(dw.data_ptr()), MN, d.N,
+                     dw.data_ptr(), out_fp32, MN, d.N,
                      (int)(R * S * C), atomic ? 1 : splits, Cpad, C);
   return dw;
 }

@@ -756,13 +756,26 @@ __global__ void xent_bwd_kernel(const scalar_t* __restrict__ logits,
 constexpr int MT_MAX_TENSORS = 32;
 constexpr int MT_CHUNK = 1 << 13;
 
+// w16[t], where not null, is a bf16 shadow of p[t] in the same memory order
+// (the conv layers' autocast copy of an fp32 weight): the kernel that produces
+// the new weight also stores its rounded copy, so no cast kernel runs per
+// forward. The rounding is the float -> bf16 conversion's round-to-nearest-
+// even, as in ATen's copy kernel.
+//
+// A tensor whose pointers are all 16-byte aligned (8 for w16) moves as
+// float4s; any other, and the last size % 4 elements, go element by element.
+// The update expression is the same text in both loops so that both contract
+// into the same three FMAs and every bit of p and m agrees between them.
 struct MTTensorList {
   float* p[MT_MAX_TENSORS];
   float* g[MT_MAX_TENSORS];
   float* m[MT_MAX_TENSORS];
+  __bf16* w16[MT_MAX_TENSORS];
   int size[MT_MAX_TENSORS];
   int ntensors;
 };
+
+typedef __attribute__((ext_vector_type(4))) __bf16 mtbf16x4;
 
 __global__ void multi_tensor_sgd_kernel(MTTensorList tl, float lr, float mu,
                                         float wd, bool has_momentum) {
@@ -780,13 +793,46 @@ __global__ void multi_tensor_sgd_kernel(MTTensorList tl, float lr, float mu,
   float* p = tl.p[t];
   float* g = tl.g[t];
   float* m = has_momentum ? tl.m[t] : nullptr;
-  for (int i = start + threadIdx.x; i < end; i += blockDim.x) {
+  __bf16* w16 = tl.w16[t];
+  const bool vec = (((size_t)p | (size_t)g | (size_t)m) & 15) == 0 &&
+                   ((size_t)w16 & 7) == 0;
+  int tail = start;   // first element of the scalar loop
+  if (vec) {
+    // start is a multiple of MT_CHUNK, so every float4 below is aligned
+    tail = start + ((end - start) & ~3);
+    for (int i = start + 4 * threadIdx.x; i < tail; i += 4 * blockDim.x) {
+      float pv[4], gv[4], mv[4];
+      *(float4*)pv = *(const float4*)(p + i);
+      *(float4*)gv = *(const float4*)(g + i);
+      if (has_momentum) *(float4*)mv = *(const float4*)(m + i);
+      #pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float grad = gv[e] + wd * pv[e];
+        if (has_momentum) {
+          grad = mu * mv[e] + grad;
+          mv[e] = grad;
+        }
+        pv[e] -= lr * grad;
+      }
+      if (has_momentum) *(float4*)(m + i) = *(float4*)mv;
+      *(float4*)(p + i) = *(float4*)pv;
+      if (w16 != nullptr) {
+        mtbf16x4 o;
+        #pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = (__bf16)pv[e];
+        *(mtbf16x4*)(w16 + i) = o;
+      }
+    }
+  }
+  for (int i = tail + threadIdx.x; i < end; i += blockDim.x) {
     float grad = g[i] + wd * p[i];
     if (has_momentum) {
       grad = mu * m[i] + grad;
       m[i] = grad;
     }
-    p[i] -= lr * grad;
+    const float pn = p[i] - lr * grad;
+    p[i] = pn;
+    if (w16 != nullptr) w16[i] = (__bf16)pn;
   }
 }
 
@@ -1738,9 +1784,12 @@ at::Tensor xent_bwd(at::Tensor logits, at::Tensor target, at::Tensor lse,
 void multi_tensor_sgd(std::vector<at::Tensor> params,
                       std::vector<at::Tensor> grads,
                       std::vector<at::Tensor> bufs,
-                      double lr, double momentum, double weight_decay) {
+                      double lr, double momentum, double weight_decay,
+                      std::vector<c10::optional<at::Tensor>> w16s) {
   const bool has_momentum = !bufs.empty();
   TORCH_CHECK(params.size() == grads.size());
+  TORCH_CHECK(w16s.empty() || w16s.size() == params.size(),
+              "multi_tensor_sgd: one w16 entry (or None) per param");
   auto stream = cur_stream();
   size_t i = 0;
   while (i < params.size()) {
@@ -1757,6 +1806,14 @@ void multi_tensor_sgd(std::vector<at::Tensor> params,
       tl.p[t] = p.data_ptr<float>();
       tl.g[t] = grads[i].data_ptr<float>();
       tl.m[t] = has_momentum ? bufs[i].data_ptr<float>() : nullptr;
+      tl.w16[t] = nullptr;
+      if (!w16s.empty() && w16s[i].has_value()) {
+        const at::Tensor& w16 = *w16s[i];
+        TORCH_CHECK(w16.is_cuda() && w16.scalar_type() == at::kBFloat16 &&
+                    w16.sizes() == p.sizes() && w16.strides() == p.strides(),
+                    "multi_tensor_sgd: w16 must be bf16 in the param's layout");
+        tl.w16[t] = reinterpret_cast<__bf16*>(w16.data_ptr());
+      }
       tl.size[t] = (int)p.numel();
       nblocks += (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
     }
@@ -1950,7 +2007,11 @@ at::Tensor conv_fwd_igemm(at::Tensor x, at::Tensor w, long stride, long pad,
 at::Tensor conv_dgrad_igemm(at::Tensor dy, at::Tensor wT, long H, long W,
                             long stride, long pad, long tile);
 at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
-                            long stride, long pad, long splits, long wtile);
+                            long stride, long pad, long splits, long wtile,
+                            bool out_fp32);
+void multi_tensor_build_wT(std::vector<at::Tensor> w16s,
+                           std::vector<at::Tensor> wTs);
+void conv_prep_weight(at::Tensor w32, at::Tensor w16, at::Tensor wT);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_build_wT", &conv_build_wT,
@@ -1966,10 +2027,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_wgrad_igemm", &conv_wgrad_igemm,
         "implicit-GEMM conv weight-grad -> bf16 channels_last (K,C,R,S); "
         "two-stage split-K, no atomics; splits 0=auto; wtile 0=auto, "
-        "1=64x128, 2=128x128, 3=256x64",
+        "1=64x128, 2=128x128, 3=256x64; out_fp32: the same bf16-rounded "
+        "values as an fp32 tensor",
         py::arg("dy"), py::arg("x"), py::arg("R"), py::arg("S"),
         py::arg("stride"), py::arg("pad"), py::arg("splits") = 0,
-        py::arg("wtile") = 0);
+        py::arg("wtile") = 0, py::arg("out_fp32") = false);
+  m.def("multi_tensor_build_wT", &multi_tensor_build_wT,
+        "wT[i] <- rotated/transposed w16[i] for every filter, one launch");
+  m.def("conv_prep_weight", &conv_prep_weight,
+        "w16 <- bf16(w32) and wT <- rotated/transposed w16, one launch");
   m.def("bn_stats", &bn_stats, "per-channel sum/sqsum (NCHW)");
   m.def("bn_stats_packed", &bn_stats_packed,
         "per-channel {sum,sqsum} packed [2C], no-atomic NHWC v2");
@@ -1997,7 +2063,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "BN backward apply from bn_bwd_tail's coeffs");
   m.def("xent_fwd", &xent_fwd, "fused softmax cross-entropy forward");
   m.def("xent_bwd", &xent_bwd, "fused softmax cross-entropy backward");
-  m.def("multi_tensor_sgd", &multi_tensor_sgd, "fused multi-tensor SGD step");
+  m.def("multi_tensor_sgd", &multi_tensor_sgd,
+        "fused multi-tensor SGD step; w16s: per-param bf16 shadow (or None) "
+        "that receives the rounded new weight",
+        py::arg("params"), py::arg("grads"), py::arg("bufs"), py::arg("lr"),
+        py::arg("momentum"), py::arg("weight_decay"),
+        py::arg("w16s") = std::vector<c10::optional<at::Tensor>>());
   m.def("multi_tensor_sgd_o2", &multi_tensor_sgd_o2,
         "fused SGD with bf16 params/grads + fp32 master (apex O2)");
   m.def("multi_tensor_unscale", &multi_tensor_unscale,

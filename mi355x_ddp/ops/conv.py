@@ -13,11 +13,28 @@ distributed.py:48): per conv shape, the GEMM-M tile (64 vs 128) for
 fwd/dgrad and the split-K factor for wgrad are measured once at first use
 with hip events and cached for the rest of the process. ``MI355X_AUTOTUNE=0``
 falls back to the static size heuristic inside the kernels.
+
+Weight shadows. Under bf16 autocast an fp32 conv weight is needed in two
+other forms: its bf16 copy (forward, wgrad) and the 180-degree-rotated
+transposed bf16 filter (dgrad). Both change only when the weight changes,
+i.e. once per optimizer step, so ``MI355Conv2d`` keeps them as persistent
+tensors (``WeightShadow``: ``w16``, ``wT``) instead of casting per forward
+and rotating per backward. ``FusedSGD`` rewrites them in the step that
+produces the new weight; any other writer is caught at the next forward by a
+``(weight._version, weight.data_ptr())`` stamp and triggers one
+``conv_prep_weight`` launch. A writer the version counter cannot see
+(``p.data.<op>_()``, raw-pointer kernels) MUST call
+``invalidate_weight_shadows``. The weight gradient comes back from the wgrad
+epilogue as fp32 (the bf16-rounded value, widened), so autograd inserts no
+cast node in either direction and results are bit-equal to the cast path.
+``MI355X_WEIGHT_SHADOWS=0`` restores the per-call casts (A/B switch);
+``MI355X_CHECK_SHADOWS=1`` verifies the shadows against a fresh cast and
+rotate at every forward (tests only: it synchronises with the host).
 """
 from __future__ import annotations
 
 import os
-from typing import Callable, Dict, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterable, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -34,11 +51,23 @@ def autotune_wanted() -> bool:
     return os.environ.get("MI355X_AUTOTUNE", "1") == "1"
 
 
+def weight_shadows_wanted() -> bool:
+    return os.environ.get("MI355X_WEIGHT_SHADOWS", "1") == "1"
+
+
+def check_shadows_wanted() -> bool:
+    return os.environ.get("MI355X_CHECK_SHADOWS", "0") == "1"
+
+
 def _native_ok(x: torch.Tensor, weight: torch.Tensor, stride, padding,
-               dilation, groups) -> bool:
+               dilation, groups, weight_dtype=None) -> bool:
+    """`weight_dtype` overrides weight.dtype: the dtype the kernels will see
+    when a bf16 shadow stands in for an fp32 weight."""
     if not native_conv_wanted() or not _backend.native_enabled(x):
         return False
-    if x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16:
+    if weight_dtype is None:
+        weight_dtype = weight.dtype
+    if x.dtype != torch.bfloat16 or weight_dtype != torch.bfloat16:
         return False
     if groups != 1 or dilation[0] != 1 or dilation[1] != 1:
         return False
@@ -130,16 +159,135 @@ def tune_report() -> str:
 MIOPEN = -1  # tuner sentinel: this pass is fastest on the MIOpen kernel
 
 
+# --------------------------------------------------------------------------
+# Persistent bf16 / rotated copies of an fp32 conv weight
+# --------------------------------------------------------------------------
+
+def rotate_wT(w16: torch.Tensor) -> torch.Tensor:
+    """Torch form of conv_build_wT: wT[c][i][j][k] = w[k][c][R-1-i][S-1-j],
+    (C, R, S, K) contiguous."""
+    return w16.flip(2, 3).permute(1, 2, 3, 0).contiguous()
+
+
+class WeightShadow:
+    """`w16` (the weight's shape and strides) and `wT` ((C,R,S,K) contiguous)
+    of one fp32 (K,C,R,S) weight. Both are allocated once and only ever
+    rewritten in place, so a hipGraph-captured step that reads or writes them
+    stays replayable. `stamp` is (weight._version, weight.data_ptr()) at the
+    time they were last written, None when known stale."""
+
+    __slots__ = ("w16", "wT", "stamp", "refreshes")
+
+    def __init__(self, weight: torch.Tensor):
+        K, C, R, S = weight.shape
+        # empty_like keeps the strides of a dense tensor
+        self.w16 = torch.empty_like(weight.detach(), dtype=torch.bfloat16)
+        self.wT = torch.empty((C, R, S, K), dtype=torch.bfloat16,
+                              device=weight.device)
+        self.stamp = None
+        self.refreshes = 0
+
+    def matches(self, weight: torch.Tensor) -> bool:
+        """These buffers can shadow `weight` (same shape, layout, device)."""
+        return (weight.dtype == torch.float32 and
+                weight.device == self.w16.device and
+                weight.shape == self.w16.shape and
+                weight.stride() == self.w16.stride())
+
+    def fresh(self, weight: torch.Tensor) -> bool:
+        return self.stamp == (weight._version, weight.data_ptr())
+
+    def mark_fresh(self, weight: torch.Tensor) -> None:
+        self.stamp = (weight._version, weight.data_ptr())
+
+    def invalidate(self) -> None:
+        self.stamp = None
+
+    def refresh(self, weight: torch.Tensor) -> None:
+        """Cast + rotate into the existing buffers (one launch natively)."""
+        w = weight.detach()
+        if _backend.native_enabled(w):
+            _backend.C().conv_prep_weight(w, self.w16, self.wT)
+        else:
+            with torch.no_grad():
+                self.w16.copy_(w)
+                self.wT.copy_(rotate_wT(self.w16))
+        self.refreshes += 1
+        self.mark_fresh(weight)
+
+    def ensure(self, weight: torch.Tensor) -> None:
+        if not self.fresh(weight):
+            self.refresh(weight)
+
+    def check(self, weight: torch.Tensor) -> None:
+        """Raise if the shadows differ from a fresh cast + rotate."""
+        w16 = weight.detach().to(torch.bfloat16)
+        if not torch.equal(self.w16, w16):
+            raise RuntimeError("stale bf16 weight shadow (w16) for a weight "
+                               f"of shape {tuple(weight.shape)}")
+        if not torch.equal(self.wT, rotate_wT(w16)):
+            raise RuntimeError("stale rotated weight shadow (wT) for a weight "
+                               f"of shape {tuple(weight.shape)}")
+
+
+def shadow_of(weight: torch.Tensor) -> Optional[WeightShadow]:
+    """The shadow attached to this parameter, if any (fresh or not)."""
+    return getattr(weight, "_mi355x_shadow", None)
+
+
+def _shadow_for(weight: torch.Tensor) -> WeightShadow:
+    """Fresh shadow of `weight`, created at first use."""
+    sh = shadow_of(weight)
+    if sh is None or not sh.matches(weight):
+        sh = WeightShadow(weight)
+        weight._mi355x_shadow = sh
+    sh.ensure(weight)
+    if check_shadows_wanted():
+        sh.check(weight)
+    return sh
+
+
+def invalidate_weight_shadows(
+        target: Union[nn.Module, torch.Tensor, Iterable[torch.Tensor]]) -> None:
+    """Mark the weight shadows of a module's (or the given) parameters stale;
+    the next forward rebuilds them. Needed after any parameter write that does
+    not bump the tensor's version counter: `p.data.<op>_()`, a collective on
+    `p.data`, a kernel writing through the raw pointer."""
+    if isinstance(target, nn.Module):
+        params = target.parameters()
+    elif isinstance(target, torch.Tensor):
+        params = (target,)
+    else:
+        params = target
+    for p in params:
+        sh = shadow_of(p)
+        if sh is not None:
+            sh.invalidate()
+
+
 class _ConvIGEMM(torch.autograd.Function):
     """Per-pass dispatch between the native igemm kernels (with their tile /
     split-K launch knobs) and MIOpen, chosen by the per-shape autotune cache.
-    The heuristic default (autotune off) is always the native kernel."""
+    The heuristic default (autotune off) is always the native kernel.
+
+    `weight` is the differentiable input. With `w16`/`wT` given (a
+    WeightShadow's tensors) it is an fp32 parameter: the passes run on the
+    shadows and backward returns an fp32 gradient. The shadows are kept on
+    ctx, not in save_for_backward: they are rewritten in place by design, and
+    backward reads whatever they hold then (the weight must not change
+    between a forward and its backward)."""
 
     @staticmethod
-    def forward(ctx, x, weight, stride: int, padding: int):
+    def forward(ctx, x, weight, stride: int, padding: int, w16=None, wT=None):
         x = x.contiguous(memory_format=torch.channels_last)
-        weight = weight.contiguous(memory_format=torch.channels_last)
-        ctx.save_for_backward(x, weight)
+        ctx.shadowed = w16 is not None
+        if ctx.shadowed:
+            weight = w16
+            ctx.save_for_backward(x)
+            ctx.w16, ctx.wT = w16, wT
+        else:
+            weight = weight.contiguous(memory_format=torch.channels_last)
+            ctx.save_for_backward(x, weight)
         ctx.stride, ctx.padding = stride, padding
         C = _backend.C()
 
@@ -153,13 +301,16 @@ class _ConvIGEMM(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
+        if ctx.shadowed:
+            (x,), weight = ctx.saved_tensors, ctx.w16
+        else:
+            x, weight = ctx.saved_tensors
         dy = dy.contiguous(memory_format=torch.channels_last)
         dx = dw = None
         C = _backend.C()
         if ctx.needs_input_grad[0]:
             # 180°-rotated, (C,R,S,K)-transposed filter for the dgrad GEMM
-            wT = C.conv_build_wT(weight)
+            wT = ctx.wT if ctx.shadowed else C.conv_build_wT(weight)
 
             def run_dx(t):
                 if t == MIOPEN:
@@ -182,12 +333,15 @@ class _ConvIGEMM(torch.autograd.Function):
                         dy, x, weight, None,
                         [ctx.stride, ctx.stride], [ctx.padding, ctx.padding],
                         [1, 1], False, [0, 0], 1, [False, True, False])[1]
-                    return g.contiguous(memory_format=torch.channels_last)
+                    g = g.contiguous(memory_format=torch.channels_last)
+                    return g.float() if ctx.shadowed else g
                 wtile, splits = c
-                # kernel emits bf16 (K,C,R,S) channels_last directly — no
-                # fp32->bf16 permute/copy pass
+                # kernel emits (K,C,R,S) channels_last directly — no
+                # fp32->bf16 permute/copy pass; for an fp32 weight the
+                # bf16-rounded values come out as fp32, no widening pass
                 return C.conv_wgrad_igemm(dy, x, R, R, ctx.stride,
-                                          ctx.padding, splits, wtile)
+                                          ctx.padding, splits, wtile,
+                                          ctx.shadowed)
 
             # two-phase: pick the tile (v1/v2 variants vs MIOpen), then the
             # split-K factor for the winning native tile
@@ -208,7 +362,7 @@ class _ConvIGEMM(torch.autograd.Function):
                     ks, tuple((tile[0], s) for s in (0, -1, 1, 32, 128)),
                     run_dw, default=tile)
             dw = run_dw(choice)
-        return dx, dw, None, None
+        return dx, dw, None, None, None, None
 
 
 def conv2d(x: torch.Tensor, weight: torch.Tensor, stride=(1, 1),
@@ -221,8 +375,12 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, stride=(1, 1),
 class MI355Conv2d(nn.Conv2d):
     """nn.Conv2d whose hot path is the implicit-GEMM HIP kernel.
 
-    Under bf16 autocast the inputs are cast explicitly (custom autograd
-    Functions are invisible to autocast's casting); outside autocast the
+    Under bf16 autocast the input is cast explicitly (custom autograd
+    Functions are invisible to autocast's casting). An fp32 channels_last
+    weight headed for the native kernels is not cast per call: its
+    WeightShadow (see the module docstring) supplies the bf16 and rotated
+    forms. Every other fp32 weight is cast per call as before, and a weight
+    that already is bf16 (`bf16_o2`) needs neither. Outside autocast the
     native path runs only when the tensors already are bf16.
     """
 
@@ -231,9 +389,22 @@ class MI355Conv2d(nn.Conv2d):
         if torch.is_autocast_enabled() and \
                 torch.get_autocast_dtype("cuda") == torch.bfloat16 and x.is_cuda:
             x = x.to(torch.bfloat16)
+            if self._shadow_ok(x, weight):
+                sh = _shadow_for(weight)
+                return _ConvIGEMM.apply(x, weight, self.stride[0],
+                                        self.padding[0], sh.w16, sh.wT)
             weight = weight.to(torch.bfloat16)
         return conv2d(x, weight, self.stride, self.padding, self.dilation,
                       self.groups)
+
+    def _shadow_ok(self, x: torch.Tensor, weight: torch.Tensor) -> bool:
+        return (weight_shadows_wanted() and
+                weight.dtype == torch.float32 and weight.is_cuda and
+                weight.dim() == 4 and
+                weight.is_contiguous(memory_format=torch.channels_last) and
+                _native_ok(x, weight, self.stride, self.padding,
+                           self.dilation, self.groups,
+                           weight_dtype=torch.bfloat16))
 
     @classmethod
     def convert(cls, module: nn.Module) -> nn.Module:

@@ -17,6 +17,15 @@ the master and the bf16 parameter is its rounded copy —
     m <- mu*m + g + wd*master ; master <- master - lr*m ; p <- bf16(master)
 
 Mixed models (some fp32, some bf16 tensors) split into the two paths.
+
+Conv weight shadows (ops/conv.py): an fp32 conv weight used under bf16
+autocast carries persistent bf16 (`w16`) and rotated (`wT`) copies. The
+native kernels here write parameters through raw pointers, which the
+tensor's version counter does not see, so for every parameter it updates
+that carries a shadow the step either rewrites the shadow itself — the SGD
+kernel stores bf16(p_new) into `w16` next to `p`, and one batched
+`multi_tensor_build_wT` launch rotates every `w16` into its `wT` — or marks
+it stale. Never neither.
 """
 from __future__ import annotations
 
@@ -25,6 +34,7 @@ from typing import List, Optional
 import torch
 
 from . import _backend
+from .conv import WeightShadow, shadow_of, weight_shadows_wanted
 
 
 class FusedSGD(torch.optim.Optimizer):
@@ -40,7 +50,7 @@ class FusedSGD(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         for group in self.param_groups:
-            p32, g32, m32 = [], [], []
+            p32, g32, m32, s32 = [], [], [], []
             p16, g16, w16, m16 = [], [], [], []
             momentum = group["momentum"]
             for p in group["params"]:
@@ -63,12 +73,14 @@ class FusedSGD(torch.optim.Optimizer):
                         state["momentum_buffer"] = torch.zeros_like(p)
                     p32.append(p)
                     g32.append(p.grad)
+                    s32.append(shadow_of(p))
                     if momentum != 0:
                         m32.append(state["momentum_buffer"])
             if p32:
                 fused_sgd_step(p32, g32, m32 if momentum != 0 else None,
                                lr=group["lr"], momentum=momentum,
-                               weight_decay=group["weight_decay"])
+                               weight_decay=group["weight_decay"],
+                               shadows=s32)
             if p16:
                 fused_sgd_o2_step(p16, g16, w16,
                                   m16 if momentum != 0 else None,
@@ -79,12 +91,36 @@ class FusedSGD(torch.optim.Optimizer):
 
 def fused_sgd_step(params: List[torch.Tensor], grads: List[torch.Tensor],
                    momentum_bufs: Optional[List[torch.Tensor]],
-                   lr: float, momentum: float, weight_decay: float) -> None:
+                   lr: float, momentum: float, weight_decay: float,
+                   shadows: Optional[List[Optional[WeightShadow]]] = None
+                   ) -> None:
+    """`shadows[i]` is params[i]'s WeightShadow or None. Each one is either
+    rewritten with the new weight here (native path) or invalidated."""
+    live = []
+    for p, sh in zip(params, shadows or ()):
+        if sh is None:
+            continue
+        if weight_shadows_wanted() and sh.matches(p):
+            live.append((p, sh))
+        else:
+            sh.invalidate()
     if params and _backend.native_enabled(params[0]):
+        w16s = []
+        if live:
+            keep = {id(sh) for _, sh in live}
+            w16s = [sh.w16 if sh is not None and id(sh) in keep else None
+                    for sh in shadows]
         _backend.C().multi_tensor_sgd(params, grads,
                                       momentum_bufs if momentum_bufs is not None else [],
-                                      lr, momentum, weight_decay)
+                                      lr, momentum, weight_decay, w16s)
+        if live:
+            _backend.C().multi_tensor_build_wT([sh.w16 for _, sh in live],
+                                               [sh.wT for _, sh in live])
+            for p, sh in live:
+                sh.mark_fresh(p)
         return
+    for _, sh in live:
+        sh.invalidate()
     # torch fallback, same math (used on CPU and for parity tests)
     for i, (p, g) in enumerate(zip(params, grads)):
         if weight_decay != 0:

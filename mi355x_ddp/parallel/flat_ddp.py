@@ -49,6 +49,8 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from ..ops.conv import invalidate_weight_shadows
+
 
 def bucket_cap_for(world_size: int, total_mb: float) -> float:
     """Gradient-bucket capacity (MB) for this world size and model size.
@@ -162,6 +164,8 @@ class FlatDDP(nn.Module):
             for t in list(self.module.parameters()) + list(self.module.buffers()):
                 if t.numel() > 0:
                     dist.broadcast(t.data, src=0, group=self.process_group)
+        # writes through .data do not bump the parameters' version counters
+        invalidate_weight_shadows(self.module)
 
     # -- overlap path ------------------------------------------------------
     def _launch_bucket(self, bi: int):
