@@ -16,7 +16,8 @@ import sysconfig
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCES = [os.path.join(REPO, "csrc", "mi355x_kernels.hip"),
-           os.path.join(REPO, "csrc", "conv_igemm.hip")]
+           os.path.join(REPO, "csrc", "conv_igemm.hip"),
+           os.path.join(REPO, "csrc", "data_aug.hip")]
 
 
 def out_path() -> str:

@@ -695,7 +695,7 @@ template <typename scalar_t>
 __global__ void xent_fwd_kernel(const scalar_t* __restrict__ logits,
                                 const long* __restrict__ target,
                                 float* __restrict__ lse_out,
-                                float* __restrict__ loss_out,
+                                float* __restrict__ row_loss,
                                 int N, int C) {
   __shared__ float lds[32];
   const int row = blockIdx.x;
@@ -725,8 +725,22 @@ __global__ void xent_fwd_kernel(const scalar_t* __restrict__ logits,
   if (threadIdx.x == 0) {
     const float lse = m + __logf(s);
     lse_out[row] = lse;
-    atomicAdd(loss_out, (lse - (float)xr[target[row]]) / N);
+    row_loss[row] = (lse - (float)xr[target[row]]) / N;
   }
+}
+
+// Sum of the per-row contributions in a fixed order (one block, strided
+// partials then the shuffle tree), so the scalar loss is the same bits for
+// the same logits (the atomicAdd per row this replaces summed in arrival
+// order and moved the last bits from run to run). It takes the place of the
+// memset that accumulator needed, so the launch count is unchanged.
+__global__ void xent_mean_kernel(const float* __restrict__ row_loss,
+                                 float* __restrict__ loss_out, int N) {
+  __shared__ float lds[32];
+  float s = 0.f;
+  for (int j = threadIdx.x; j < N; j += blockDim.x) s += row_loss[j];
+  s = block_reduce_sum(s, lds);
+  if (threadIdx.x == 0) *loss_out = s;
 }
 
 template <typename scalar_t>
@@ -1750,15 +1764,18 @@ std::vector<at::Tensor> xent_fwd(at::Tensor logits, at::Tensor target) {
   TORCH_CHECK(target.scalar_type() == at::kLong, "target must be int64");
   const int N = logits.size(0), C = logits.size(1);
   auto lse = at::empty({N}, logits.options().dtype(at::kFloat));
-  auto loss = at::zeros({}, logits.options().dtype(at::kFloat));
+  auto row_loss = at::empty({N}, logits.options().dtype(at::kFloat));
+  auto loss = at::empty({}, logits.options().dtype(at::kFloat));
   const int threads = C <= 128 ? 64 : 256;
   AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::Half, at::ScalarType::BFloat16,
       logits.scalar_type(), "xent_fwd", [&] {
     hipLaunchKernelGGL(xent_fwd_kernel<scalar_t>, dim3(N), dim3(threads), 0,
                        cur_stream(),
                        logits.data_ptr<scalar_t>(), target.data_ptr<long>(),
-                       lse.data_ptr<float>(), loss.data_ptr<float>(), N, C);
+                       lse.data_ptr<float>(), row_loss.data_ptr<float>(), N, C);
   });
+  hipLaunchKernelGGL(xent_mean_kernel, dim3(1), dim3(256), 0, cur_stream(),
+                     row_loss.data_ptr<float>(), loss.data_ptr<float>(), N);
   return {loss, lse};
 }
 
@@ -2013,6 +2030,12 @@ void multi_tensor_build_wT(std::vector<at::Tensor> w16s,
                            std::vector<at::Tensor> wTs);
 void conv_prep_weight(at::Tensor w32, at::Tensor w16, at::Tensor wT);
 
+// csrc/data_aug.hip — device-resident input pipeline (crop/flip/normalize)
+std::tuple<at::Tensor, at::Tensor> batch_augment(
+    at::Tensor images_u8, at::Tensor labels_i64, at::Tensor idx_i32,
+    c10::optional<at::Tensor> aug_i32, at::Tensor lut_f32, long pad,
+    bool channels_last, at::ScalarType out_dtype);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_build_wT", &conv_build_wT,
         "build rotated/transposed filter for dgrad (one launch)");
@@ -2079,4 +2102,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "NHWC max pool forward -> (y, argmax idx)");
   m.def("maxpool_bwd", &maxpool_bwd, "NHWC max pool backward (gather)");
   m.def("class_rank", &class_rank, "per-row rank of target class (for top-k)");
+  m.def("batch_augment", &batch_augment,
+        "uint8 NHWC dataset + batch indices -> (images, labels): zero-padded "
+        "crop, flip, table normalize and cast in one launch; aug None = eval",
+        py::arg("images_u8"), py::arg("labels_i64"), py::arg("idx_i32"),
+        py::arg("aug_i32"), py::arg("lut_f32"), py::arg("pad"),
+        py::arg("channels_last"), py::arg("out_dtype"));
 }

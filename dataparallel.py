@@ -41,8 +41,11 @@ def run(args, amp_default="fp32"):
         cfg, device, world_size=1, rank=0, distributed=False, wrap="none")
     if torch.cuda.is_available() and torch.cuda.device_count() > 1:
         model = wrap_data_parallel(model, list(range(torch.cuda.device_count())))
-    train_loader, test_loader, _ = build_loaders(cfg, 1, 0, distributed=False)
-    fit(model, train_loader, test_loader, None, criterion, optimizer,
+    # the third slot is None here unless --device_data, whose loader wants
+    # set_epoch from fit to redraw its crops
+    train_loader, test_loader, sampler = build_loaders(
+        cfg, 1, 0, distributed=False, device=device)
+    fit(model, train_loader, test_loader, sampler, criterion, optimizer,
         scheduler, cfg, device, scaler=scaler)
 
 

@@ -66,6 +66,11 @@ class TrainConfig:
     num_workers: int = 4
     pin_memory: bool = True
     seed: int = 0
+    # dataset resident on the GPU as uint8, one fused crop/normalize launch
+    # per batch instead of the DataLoader (data/device.py); hflip adds a
+    # random horizontal flip and exists on that path only
+    device_data: bool = False
+    hflip: bool = False
 
     # native kernels
     native_ops: bool = True           # HIP kernels when extension present; fail loudly on GPU if absent
@@ -83,6 +88,11 @@ class TrainConfig:
     # step caps (None = full epoch); used by smoke tests and quick CLI runs
     max_train_steps: Optional[int] = None
     max_eval_steps: Optional[int] = None
+
+    def __post_init__(self):
+        if self.hflip and not self.device_data:
+            raise ValueError("hflip needs device_data: the DataLoader path "
+                             "has no flip and would ignore it silently")
 
     def per_rank_batch(self, world_size: int) -> int:
         return max(1, self.batch_size // max(1, world_size))
@@ -131,6 +141,12 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--warmup_epochs", default=None, type=int)
     p.add_argument("--evaluate", action="store_true",
                    help="run validation only (use with --resume)")
+    p.add_argument("--device_data", "--device-data", dest="device_data",
+                   action="store_true",
+                   help="keep the dataset on the GPU as uint8; one fused "
+                        "crop/normalize kernel launch per batch")
+    p.add_argument("--hflip", action="store_true",
+                   help="random horizontal flip (needs --device_data)")
     return p
 
 
@@ -168,5 +184,9 @@ def config_from_args(args: argparse.Namespace, **overrides) -> TrainConfig:
         kw["evaluate"] = True
     if getattr(args, "channels_last", None) is not None:
         kw["channels_last"] = bool(args.channels_last)
+    if getattr(args, "device_data", False):
+        kw["device_data"] = True
+    if getattr(args, "hflip", False):
+        kw["hflip"] = True
     kw.update(overrides)
     return TrainConfig(**kw)

@@ -128,7 +128,7 @@ def main_worker(local_rank: int, nprocs: int, cfg: TrainConfig,
         if dist_utils.is_main_process():
             print(f"resumed from {cfg.resume} at epoch {start_epoch}")
     train_loader, test_loader, train_sampler = build_loaders(
-        cfg, nprocs, rank, distributed=nprocs > 1)
+        cfg, nprocs, rank, distributed=nprocs > 1, device=device)
     if cfg.evaluate:
         from .engine import validate
         best = validate(model, test_loader, criterion, device, cfg)

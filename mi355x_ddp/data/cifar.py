@@ -121,13 +121,20 @@ def build_datasets(cfg: TrainConfig) -> Tuple[Dataset, Dataset]:
 
 
 def build_loaders(cfg: TrainConfig, world_size: int, rank: int,
-                  distributed: bool = True,
+                  distributed: bool = True, device=None,
                   ) -> Tuple[DataLoader, DataLoader, Optional[DistributedSampler]]:
     """Sharded train/test loaders. Global batch is divided by world size
     (reference distributed.py:67); both loaders get a DistributedSampler in
     distributed mode (reference distributed.py:70-75 — note the test-set
     sampler pads to divide evenly, so eval accuracy is approximate there too);
-    train uses drop_last so every rank steps the same count."""
+    train uses drop_last so every rank steps the same count.
+
+    With ``cfg.device_data`` the dataset is resident on ``device`` and the
+    result is ``(train DeviceLoader, test DeviceLoader, train DeviceLoader)``
+    (data/device.py); the third slot takes ``set_epoch`` like a sampler."""
+    if cfg.device_data:
+        from .device import build_device_loaders
+        return build_device_loaders(cfg, world_size, rank, device)
     train_ds, test_ds = build_datasets(cfg)
     per_rank = cfg.per_rank_batch(world_size)
     train_sampler: Optional[DistributedSampler] = None
