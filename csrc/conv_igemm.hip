@@ -1,4 +1,6 @@
-// MI355X (gfx950/CDNA4) implicit-GEMM convolution kernels — NHWC bf16.
+// MI355X (gfx950/CDNA4) implicit-GEMM convolution kernels — NHWC bf16 or
+// fp16 (every kernel that computes is templated on the element type, see
+// Elem16; "bf16" in the comments below stands for either format).
 //
 // Replaces the reference's dependency on cuDNN conv kernels (SURVEY.md §2.2
 // N1: 3x3 s1/s2 and 1x1 convs of the CIFAR ResNet, fwd + dgrad + wgrad).
@@ -33,8 +35,37 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+// The 16-bit element format of a kernel: __bf16 or _Float16. Staging, LDS
+// layout, transposes and slabs move 16-bit patterns whatever they hold; the
+// format decides only the x8 operand type, the MFMA instruction
+// (v_mfma_f32_16x16x32_{bf16,f16}: same operand layout, 8 elements per lane
+// for A and B, f32x4 for C/D) and the float -> element rounding. Both
+// conversions are plain round-to-nearest-even; fp16 does not saturate: a
+// value beyond 65504 becomes +-inf and NaN stays NaN, as in ATen and MIOpen,
+// which is what a loss scaler's inf check relies on.
+template <typename T> struct Elem16;
+
+template <> struct Elem16<__bf16> {
+  typedef __attribute__((ext_vector_type(8))) __bf16 x8;
+  static __device__ __forceinline__ f32x4 mfma(x8 a, x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ __bf16 from_float(float v) {
+    return (__bf16)v;
+  }
+};
+
+template <> struct Elem16<_Float16> {
+  typedef __attribute__((ext_vector_type(8))) _Float16 x8;
+  static __device__ __forceinline__ f32x4 mfma(x8 a, x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ _Float16 from_float(float v) {
+    return (_Float16)v;
+  }
+};
 
 constexpr int BM = 128;   // GEMM M tile (output pixels)
 constexpr int BN = 64;    // GEMM N tile (output channels / rsc)
@@ -104,18 +135,20 @@ __device__ __forceinline__ void decode_m2(int m, const ConvDims& d,
 // with it the per-pass re-reads of the gathered A operand — for the wide-N
 // high-C shapes (ResNet50's 1x1 expansions), where fwd/dgrad is A-traffic
 // bound.
-template <int MODE, bool FAST, int BMT = BM, bool PADC = false, int BNT = BN>
+template <typename T, int MODE, bool FAST, int BMT = BM, bool PADC = false,
+          int BNT = BN>
 __global__ __launch_bounds__(256)
-void conv_igemm_kernel(const __bf16* __restrict__ Ag,
-                       const __bf16* __restrict__ Bg,
-                       __bf16* __restrict__ out, ConvDims d) {
+void conv_igemm_kernel(const T* __restrict__ Ag,
+                       const T* __restrict__ Bg,
+                       T* __restrict__ out, ConvDims d) {
+  typedef typename Elem16<T>::x8 x8;
   constexpr int MI = BMT / 32;
   constexpr int NI = BNT / 32;
   constexpr int EPT = BMT / 4;          // 32 or 16 elems per loader thread
   constexpr int PER_ROW = 64 / EPT;     // loader threads per A row
   constexpr int BEPT = BK * BNT / 256;  // B elems per loader thread
-  __shared__ __bf16 sA[BMT * LDK];
-  __shared__ __bf16 sB[BNT * LDK];
+  __shared__ T sA[BMT * LDK];
+  __shared__ T sB[BNT * LDK];
 
   const int tid = threadIdx.x;
   const int m0 = blockIdx.y * BMT;
@@ -204,19 +237,18 @@ void conv_igemm_kernel(const __bf16* __restrict__ Ag,
   auto mfma_tile = [&]() {
     #pragma unroll
     for (int ks = 0; ks < BK; ks += 32) {
-      bf16x8 af[MI], bf[NI];
+      x8 af[MI], bf[NI];
       #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
-        af[mi] = *(const bf16x8*)&sA[(wm + mi * 16 + fr) * LDK + ks + fk];
+        af[mi] = *(const x8*)&sA[(wm + mi * 16 + fr) * LDK + ks + fk];
       #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
-        bf[ni] = *(const bf16x8*)&sB[(wn + ni * 16 + fr) * LDK + ks + fk];
+        bf[ni] = *(const x8*)&sB[(wn + ni * 16 + fr) * LDK + ks + fk];
       #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
         #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              af[mi], bf[ni], acc[mi][ni], 0, 0, 0);
+          acc[mi][ni] = Elem16<T>::mfma(af[mi], bf[ni], acc[mi][ni]);
     }
   };
 
@@ -300,7 +332,7 @@ void conv_igemm_kernel(const __bf16* __restrict__ Ag,
         // generic gather: one element at a time (stem conv only)
         for (int e = tid; e < BMT * BK; e += 256) {
           const int row = e >> 6, kk = kk0 + (e & 63);
-          __bf16 v = (__bf16)0.f;
+          T v = (T)0.f;
           if (kk < d.K) {
             int m = m0 + row;
             if (m >= d.M) m = d.M - 1;
@@ -318,7 +350,7 @@ void conv_igemm_kernel(const __bf16* __restrict__ Ag,
         for (int e = tid; e < BNT * BK; e += 256) {
           const int row = e >> 6, kk = kk0 + (e & 63);
           sB[row * LDK + (e & 63)] = (kk < d.K)
-              ? Bg[(long)min(n0 + row, d.N - 1) * d.K + kk] : (__bf16)0.f;
+              ? Bg[(long)min(n0 + row, d.N - 1) * d.K + kk] : (T)0.f;
         }
       }
       __syncthreads();
@@ -346,7 +378,7 @@ void conv_igemm_kernel(const __bf16* __restrict__ Ag,
           decode_m2(m, d, pa, pb, on, ooh, oow);
           om = ((long)on * d.OH + ooh) * d.OW + oow;
         }
-        out[om * d.N + n] = (__bf16)acc[mi][ni][r];
+        out[om * d.N + n] = Elem16<T>::from_float(acc[mi][ni][r]);
       }
     }
   }
@@ -381,14 +413,16 @@ void conv_igemm_kernel(const __bf16* __restrict__ Ag,
 // instruction). A tile's region is TM*TN floats, edge tiles included: their
 // out-of-range rows/columns are stored as accumulated and dropped by
 // wgrad_reduce_frag_kernel, which undoes the permutation.
-// Every dw element leaves through here. The value is rounded to bf16 either
-// way; f32 stores that rounded value widened (exact), for an fp32 parameter
-// whose gradient would otherwise be widened by a separate cast kernel.
+// Every dw element leaves through here. The value is rounded to the element
+// format T either way; f32 stores that rounded value widened (exact), for an
+// fp32 parameter whose gradient would otherwise be widened by a separate cast
+// kernel. An fp16 overflow therefore arrives as inf in the fp32 gradient too.
+template <typename T>
 __device__ __forceinline__ void store_dw(void* __restrict__ dw, bool f32,
                                          long idx, float v) {
-  const __bf16 b = (__bf16)v;
+  const T b = Elem16<T>::from_float(v);
   if (f32) ((float*)dw)[idx] = (float)b;
-  else ((__bf16*)dw)[idx] = b;
+  else ((T*)dw)[idx] = b;
 }
 
 template <int NF>
@@ -401,19 +435,20 @@ __device__ __forceinline__ void store_frag_slab(float* __restrict__ dwp,
   for (int f = 0; f < NF; ++f) dst[f * 256] = acc[f];
 }
 
-template <bool FAST, bool PADC = false, bool DIRECT = false,
+template <typename T, bool FAST, bool PADC = false, bool DIRECT = false,
           bool ATOMIC = false>
 __global__ __launch_bounds__(256)
-void conv_wgrad_kernel(const __bf16* __restrict__ dy,
-                       const __bf16* __restrict__ x,
+void conv_wgrad_kernel(const T* __restrict__ dy,
+                       const T* __restrict__ x,
                        float* __restrict__ dwp,
                        void* __restrict__ dwb, ConvDims d, bool f32) {
+  typedef typename Elem16<T>::x8 x8;
   // d: M = Kout, N = R*S*C, K = Nb*P*Q; OH/OW = P,Q; GH/GW/GC = H,W,C
   // 64(Kout) x 128(rsc) tile: each loaded byte feeds twice the MFMA work of
   // the 64x64 tile. FAST needs C % 64 == 0 so every 32-wide rsc sub-chunk
   // stays inside one (r,s) filter tap.
-  __shared__ __bf16 sA[64 * LDK];   // [kout][npq]
-  __shared__ __bf16 sB[128 * LDK];  // [rsc][npq]
+  __shared__ T sA[64 * LDK];   // [kout][npq]
+  __shared__ T sB[128 * LDK];  // [rsc][npq]
 
   const int tid = threadIdx.x;
   const int m0 = blockIdx.y * 64;
@@ -442,7 +477,7 @@ void conv_wgrad_kernel(const __bf16* __restrict__ dy,
     // ---- dy tile, transposed into sA[kout][npq] ------------------------
     {
       const int cg = grp * 16;
-      __bf16 vals[16];
+      T vals[16];
       // the row bound also guards FAST: K % 16 == 0 admits K % 64 != 0
       // (e.g. K=80 via the public conv2d API), where the last tile's 16-wide
       // float4 loads would run past dy
@@ -454,7 +489,7 @@ void conv_wgrad_kernel(const __bf16* __restrict__ dy,
         #pragma unroll
         for (int e = 0; e < 16; ++e)
           vals[e] = (npq_ok && m0 + cg + e < d.M)
-              ? dy[(long)npq * d.M + m0 + cg + e] : (__bf16)0.f;
+              ? dy[(long)npq * d.M + m0 + cg + e] : (T)0.f;
       }
       #pragma unroll
       for (int e = 0; e < 16; ++e)
@@ -463,7 +498,7 @@ void conv_wgrad_kernel(const __bf16* __restrict__ dy,
     // ---- x tile (128 rsc cols = 4 x 32-col sub-chunks), transposed -----
     {
       const int cg = grp * 32;     // this thread's 32-col sub-chunk
-      __bf16 vals[32];
+      T vals[32];
       if (PADC) {
         // stem: 8 taps of 4 padded channels each, aligned dwordx2 gathers
         #pragma unroll
@@ -498,13 +533,13 @@ void conv_wgrad_kernel(const __bf16* __restrict__ dy,
           *(float4*)&vals[24] = src[3];
         } else {
           #pragma unroll
-          for (int e = 0; e < 32; ++e) vals[e] = (__bf16)0.f;
+          for (int e = 0; e < 32; ++e) vals[e] = (T)0.f;
         }
       } else {
         #pragma unroll
         for (int e = 0; e < 32; ++e) {
           const int nn = n0 + cg + e;
-          __bf16 v = (__bf16)0.f;
+          T v = (T)0.f;
           if (npq_ok && nn < d.N) {
             const int i = nn / SC, rem = nn - i * SC;
             const int j = rem / d.GC, c = rem - j * d.GC;
@@ -524,19 +559,18 @@ void conv_wgrad_kernel(const __bf16* __restrict__ dy,
 
     #pragma unroll
     for (int ks = 0; ks < BK; ks += 32) {
-      bf16x8 af[2], bf[4];
+      x8 af[2], bf[4];
       #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
-        af[mi] = *(const bf16x8*)&sA[(wm + mi * 16 + fr) * LDK + ks + fk];
+        af[mi] = *(const x8*)&sA[(wm + mi * 16 + fr) * LDK + ks + fk];
       #pragma unroll
       for (int ni = 0; ni < 4; ++ni)
-        bf[ni] = *(const bf16x8*)&sB[(wn + ni * 16 + fr) * LDK + ks + fk];
+        bf[ni] = *(const x8*)&sB[(wn + ni * 16 + fr) * LDK + ks + fk];
       #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
         #pragma unroll
         for (int ni = 0; ni < 4; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              af[mi], bf[ni], acc[mi][ni], 0, 0, 0);
+          acc[mi][ni] = Elem16<T>::mfma(af[mi], bf[ni], acc[mi][ni]);
     }
     __syncthreads();
   }
@@ -559,7 +593,7 @@ void conv_wgrad_kernel(const __bf16* __restrict__ dy,
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + wm + mi * 16 + dm + r;
         if (m >= d.M) continue;
-        if (DIRECT) store_dw(dwb, f32, (long)m * d.N + n, acc[mi][ni][r]);
+        if (DIRECT) store_dw<T>(dwb, f32, (long)m * d.N + n, acc[mi][ni][r]);
         else if (ATOMIC) atomicAdd(&slab[(long)m * d.N + n], acc[mi][ni][r]);
         else slab[(long)m * d.N + n] = acc[mi][ni][r];
       }
@@ -596,20 +630,21 @@ __device__ __forceinline__ void tr4x4_bf16(const uint2 in[4], uint2 out[4]) {
 // left CH=1 at 54-57% SQ_WAIT_ANY (profiles/r2c13): LDS doubles (69.6 KB
 // for (2,2) -> 2 blocks/CU) and staging registers double, trading
 // block-level overlap for complete within-wave latency cover.
-template <int WGM, int WGN, bool DIRECT, int CH = 1>
+template <typename T, int WGM, int WGN, bool DIRECT, int CH = 1>
 __global__ __launch_bounds__(256, 2)
-void conv_wgrad_v2_kernel(const __bf16* __restrict__ dy,
-                          const __bf16* __restrict__ x,
+void conv_wgrad_v2_kernel(const T* __restrict__ dy,
+                          const T* __restrict__ x,
                           float* __restrict__ dwp,
                           void* __restrict__ dwb, ConvDims d, bool f32) {
+  typedef typename Elem16<T>::x8 x8;
   constexpr int TM = WGM * 64;          // kout tile
   constexpr int TN = WGN * 64;          // rsc tile
   constexpr int TA = TM / 64;
   constexpr int TB = TN / 64;
   constexpr int SK = CH * BK;           // npq rows per stage
   constexpr int SLDK = SK + 8;          // padded LDS row length
-  __shared__ __bf16 sA[TM * SLDK];      // [kout][npq]
-  __shared__ __bf16 sB[TN * SLDK];      // [rsc][npq]
+  __shared__ T sA[TM * SLDK];      // [kout][npq]
+  __shared__ T sB[TN * SLDK];      // [rsc][npq]
   // DOUBLE-BUFFERED per-chunk row metadata: for npq row r, the x base
   // offset of tap (0,0), the (ih0, iw0) coords for bounds tests, and a
   // validity flag (NOT derived from the offset sign — that offset is
@@ -673,7 +708,7 @@ void conv_wgrad_v2_kernel(const __bf16* __restrict__ dy,
       } else {
         #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          __bf16 e[4] = {};
+          T e[4] = {};
           if (npq0 + i < d.K)
             #pragma unroll
             for (int c = 0; c < 4; ++c)
@@ -741,25 +776,24 @@ void conv_wgrad_v2_kernel(const __bf16* __restrict__ dy,
   auto mfma_all = [&]() {
     #pragma unroll
     for (int ks = 0; ks < SK; ks += 32) {
-      bf16x8 af[4], bf[4];
+      x8 af[4], bf[4];
       #pragma unroll
       for (int mi = 0; mi < 4; ++mi) {
         const int row = wm + mi * 16 + fr;
         const int q = ((ks + fk) >> 2) ^ ((row >> 2) & 14);
-        af[mi] = *(const bf16x8*)&sA[row * SLDK + q * 4];
+        af[mi] = *(const x8*)&sA[row * SLDK + q * 4];
       }
       #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const int row = wn + ni * 16 + fr;
         const int q = ((ks + fk) >> 2) ^ ((row >> 2) & 14);
-        bf[ni] = *(const bf16x8*)&sB[row * SLDK + q * 4];
+        bf[ni] = *(const x8*)&sB[row * SLDK + q * 4];
       }
       #pragma unroll
       for (int mi = 0; mi < 4; ++mi)
         #pragma unroll
         for (int ni = 0; ni < 4; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              af[mi], bf[ni], acc[mi][ni], 0, 0, 0);
+          acc[mi][ni] = Elem16<T>::mfma(af[mi], bf[ni], acc[mi][ni]);
     }
   };
 
@@ -808,7 +842,7 @@ void conv_wgrad_v2_kernel(const __bf16* __restrict__ dy,
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + wm + mi * 16 + dm + r;
         if (m >= d.M) continue;
-        store_dw(dwb, f32, (long)m * d.N + n, acc[mi][ni][r]);
+        store_dw<T>(dwb, f32, (long)m * d.N + n, acc[mi][ni][r]);
       }
     }
 }
@@ -821,19 +855,20 @@ void conv_wgrad_v2_kernel(const __bf16* __restrict__ dy,
 // before chunk k's MFMAs, hiding the ~900-cycle HBM latency that left v2 at
 // ~38% of peak bandwidth). Tile = (WGM*64) x (WGN*64), 2 barriers/chunk.
 // ---------------------------------------------------------------------------
-template <int WGM, int WGN, bool DIRECT>
+template <typename T, int WGM, int WGN, bool DIRECT>
 __global__ __launch_bounds__(256, 2)  // 2 waves/SIMD: the double buffer
                                       // needs a partner wave per SIMD
-void conv_wgrad_lin_kernel(const __bf16* __restrict__ dy,
-                           const __bf16* __restrict__ x,
+void conv_wgrad_lin_kernel(const T* __restrict__ dy,
+                           const T* __restrict__ x,
                            float* __restrict__ dwp,
                            void* __restrict__ dwb, ConvDims d, bool f32) {
+  typedef typename Elem16<T>::x8 x8;
   constexpr int TM = WGM * 64;
   constexpr int TN = WGN * 64;
   constexpr int TA = TM / 64;
   constexpr int TB = TN / 64;
-  __shared__ __bf16 sA[TM * LDK];
-  __shared__ __bf16 sB[TN * LDK];
+  __shared__ T sA[TM * LDK];
+  __shared__ T sB[TN * LDK];
 
   const int tid = threadIdx.x;
   const int m0 = blockIdx.y * TM;
@@ -854,7 +889,7 @@ void conv_wgrad_lin_kernel(const __bf16* __restrict__ dy,
   uint2 sta[TA][4], stb[TB][4];
 
   // per-pass block decomposition (c4-fastest => coalesced loads)
-  auto load_op = [&](const __bf16* src, int ncols, int c4n, int base,
+  auto load_op = [&](const T* src, int ncols, int c4n, int base,
                      int kk0, int bid, uint2 (&in)[4]) {
     const int c4 = bid & (c4n - 1);
     const int r4 = bid / c4n;
@@ -867,7 +902,7 @@ void conv_wgrad_lin_kernel(const __bf16* __restrict__ dy,
     } else {
       #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        __bf16 e[4] = {};
+        T e[4] = {};
         if (row0 + i < d.K)
           #pragma unroll
           for (int c = 0; c < 4; ++c)
@@ -913,25 +948,24 @@ void conv_wgrad_lin_kernel(const __bf16* __restrict__ dy,
   auto mfma_all = [&]() {
     #pragma unroll
     for (int ks = 0; ks < BK; ks += 32) {
-      bf16x8 af[4], bf[4];
+      x8 af[4], bf[4];
       #pragma unroll
       for (int mi = 0; mi < 4; ++mi) {
         const int row = wm + mi * 16 + fr;
         const int q = ((ks + fk) >> 2) ^ ((row >> 2) & 14);
-        af[mi] = *(const bf16x8*)&sA[row * LDK + q * 4];
+        af[mi] = *(const x8*)&sA[row * LDK + q * 4];
       }
       #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const int row = wn + ni * 16 + fr;
         const int q = ((ks + fk) >> 2) ^ ((row >> 2) & 14);
-        bf[ni] = *(const bf16x8*)&sB[row * LDK + q * 4];
+        bf[ni] = *(const x8*)&sB[row * LDK + q * 4];
       }
       #pragma unroll
       for (int mi = 0; mi < 4; ++mi)
         #pragma unroll
         for (int ni = 0; ni < 4; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              af[mi], bf[ni], acc[mi][ni], 0, 0, 0);
+          acc[mi][ni] = Elem16<T>::mfma(af[mi], bf[ni], acc[mi][ni]);
     }
   };
 
@@ -972,15 +1006,16 @@ void conv_wgrad_lin_kernel(const __bf16* __restrict__ dy,
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + wm + mi * 16 + dm + r;
         if (m >= d.M) continue;
-        store_dw(dwb, f32, (long)m * d.N + n, acc[mi][ni][r]);
+        store_dw<T>(dwb, f32, (long)m * d.N + n, acc[mi][ni][r]);
       }
     }
 }
 
-// Sum the split-K partial slabs and emit the bf16 channels_last weight grad:
+// Sum the split-K partial slabs and emit the 16-bit channels_last weight grad:
 // out[k][tap*Cout + c] (= memory layout of channels_last (K, Cout, R, S)).
 // Cpad==Cout -> identity column map; the stem maps Cpad=4 -> Cout=3 and drops
 // the zero-pad channel and any tap >= R*S.
+template <typename T>
 __global__ void wgrad_reduce_kernel(const float* __restrict__ part,
                                     void* __restrict__ dw, bool f32,
                                     long MN, int N, int Nout, int splits,
@@ -997,7 +1032,7 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ part,
     }
     float s = 0.f;
     for (int z = 0; z < splits; ++z) s += part[(long)z * MN + o];
-    store_dw(dw, f32, m * Nout + nout, s);
+    store_dw<T>(dw, f32, m * Nout + nout, s);
   }
 }
 
@@ -1026,7 +1061,7 @@ __device__ __forceinline__ f32x4 ld_frag(const float* p) {
   else return f32x4{*p, 0.f, 0.f, 0.f};
 }
 
-template <int ZW, int V>
+template <typename T, int ZW, int V>
 __global__ __launch_bounds__(256)
 void wgrad_reduce_frag_kernel(const float* __restrict__ part,
                               void* __restrict__ dw, bool f32, int M, int N,
@@ -1093,12 +1128,15 @@ void wgrad_reduce_frag_kernel(const float* __restrict__ part,
   #pragma unroll
   for (int r = 0; r < V; ++r)
     if (m + r0 + r < M)
-      store_dw(dw, f32, (long)(m + r0 + r) * Nout + nout, s[r]);
+      store_dw<T>(dw, f32, (long)(m + r0 + r) * Nout + nout, s[r]);
 }
 
 // wT[c][i][j][k] = w[k][R-1-i][S-1-j][c] — the 180°-rotated transposed filter
 // the dgrad GEMM consumes, built in ONE kernel (the ATen flip+permute+copy
-// chain was 3 launches per conv backward).
+// chain was 3 launches per conv backward). This kernel, the 16-bit source path
+// of multi_build_wT_kernel and the two stem pad kernels below only copy
+// 16-bit patterns (and write zero, all bits clear in either format): they are
+// declared on __bf16 and take fp16 tensors through the same instantiation.
 __global__ void build_wT_kernel(const __bf16* __restrict__ w,
                                 __bf16* __restrict__ wT,
                                 int K, int R, int S, int C) {
@@ -1118,9 +1156,10 @@ __global__ void build_wT_kernel(const __bf16* __restrict__ w,
 // transpose: a block takes one filter tap of one tensor, 64 k x 64 c. It
 // reads 64 rows of 64 consecutive c (128 B of bf16 each) and writes 64 rows
 // of 64 consecutive k (128 B each), where build_wT_kernel reads 2 bytes at
-// stride R*S*C per lane. IT = float additionally rounds to bf16 and, where
-// w16 is given, stores the rounded copy at the source index: cast + rotate of
-// an fp32 weight in one pass (conv_prep_weight). Rows move as 16-byte units
+// stride R*S*C per lane. IT = float additionally rounds to OT (bf16 or fp16)
+// and, where w16 is given, stores the rounded copy at the source index: cast
+// + rotate of an fp32 weight in one pass (conv_prep_weight). A 16-bit IT is
+// moved as it is, whichever format it holds. Rows move as 16-byte units
 // when the row length is a multiple of 8 and the base is 16-byte aligned, and
 // element by element otherwise (ragged C such as the 3-channel stem); either
 // way consecutive lanes touch consecutive addresses, and K or C past the last
@@ -1129,21 +1168,23 @@ constexpr int WT_MAX_TENSORS = 32;
 
 struct WTList {
   const void* w[WT_MAX_TENSORS];   // [K][R*S][C], IT
-  __bf16* w16[WT_MAX_TENSORS];     // [K][R*S][C] bf16 copy of w, or null
-  __bf16* wT[WT_MAX_TENSORS];      // [C][R*S][K]
+  void* w16[WT_MAX_TENSORS];       // [K][R*S][C] 16-bit copy of w, or null
+  void* wT[WT_MAX_TENSORS];        // [C][R*S][K], 16-bit
   int K[WT_MAX_TENSORS], C[WT_MAX_TENSORS], RS[WT_MAX_TENSORS];
   int nblocks[WT_MAX_TENSORS];     // RS * ceil(K/64) * ceil(C/64)
   int ntensors;
 };
 
+template <typename OT>
 __device__ __forceinline__ unsigned short wt_bits(float v) {
-  return __builtin_bit_cast(unsigned short, (__bf16)v);
+  return __builtin_bit_cast(unsigned short, Elem16<OT>::from_float(v));
 }
+template <typename OT>
 __device__ __forceinline__ unsigned short wt_bits(__bf16 v) {
   return __builtin_bit_cast(unsigned short, v);
 }
 
-template <typename IT>
+template <typename IT, typename OT = __bf16>
 __global__ __launch_bounds__(256)
 void multi_build_wT_kernel(WTList tl) {
   // [k][c]; 33-dword rows keep the column reads of the store phase off the
@@ -1180,10 +1221,10 @@ void multi_build_wT_kernel(WTList tl) {
       if constexpr (sizeof(IT) == 4) {
         const float4 a = *(const float4*)(w + idx);
         const float4 bb = *(const float4*)(w + idx + 4);
-        v.x = wt_bits(a.x) | ((unsigned)wt_bits(a.y) << 16);
-        v.y = wt_bits(a.z) | ((unsigned)wt_bits(a.w) << 16);
-        v.z = wt_bits(bb.x) | ((unsigned)wt_bits(bb.y) << 16);
-        v.w = wt_bits(bb.z) | ((unsigned)wt_bits(bb.w) << 16);
+        v.x = wt_bits<OT>(a.x) | ((unsigned)wt_bits<OT>(a.y) << 16);
+        v.y = wt_bits<OT>(a.z) | ((unsigned)wt_bits<OT>(a.w) << 16);
+        v.z = wt_bits<OT>(bb.x) | ((unsigned)wt_bits<OT>(bb.y) << 16);
+        v.w = wt_bits<OT>(bb.z) | ((unsigned)wt_bits<OT>(bb.w) << 16);
         if (w16 != nullptr) *(uint4*)(w16 + idx) = v;
       } else {
         v = *(const uint4*)(w + idx);
@@ -1199,7 +1240,7 @@ void multi_build_wT_kernel(WTList tl) {
       const int k = k0 + kk, c = c0 + cc;
       if (k >= K || c >= C) continue;
       const long idx = ((long)k * RS + tap) * C + c;
-      const unsigned short bits = wt_bits(w[idx]);
+      const unsigned short bits = wt_bits<OT>(w[idx]);
       if (sizeof(IT) == 4 && w16 != nullptr) w16[idx] = bits;
       tile[kk][cc] = bits;
     }
@@ -1278,23 +1319,43 @@ __global__ void pad_w_c4_kernel(const __bf16* __restrict__ w,
 
 hipStream_t conv_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
-inline void check_nhwc_bf16(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::ScalarType::BFloat16,
-              name, " must be a bf16 HIP tensor");
+inline bool is_16bit(const at::Tensor& t) {
+  return t.scalar_type() == at::ScalarType::BFloat16 ||
+         t.scalar_type() == at::ScalarType::Half;
+}
+
+inline void check_nhwc_16(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && is_16bit(t),
+              name, " must be a bf16 or fp16 HIP tensor, got ",
+              t.scalar_type());
   TORCH_CHECK(t.dim() == 4 &&
               (t.is_contiguous(at::MemoryFormat::ChannelsLast) ||
                t.is_contiguous()),
               name, " must be 4-D and dense");
 }
 
+// All 16-bit operands of one call share one format.
+inline void check_same_16(const at::Tensor& a, const char* an,
+                          const at::Tensor& b, const char* bn) {
+  TORCH_CHECK(a.scalar_type() == b.scalar_type(), an, " is ", a.scalar_type(),
+              " but ", bn, " is ", b.scalar_type(),
+              ": the 16-bit operands of a conv call must share one dtype");
+}
+
+// Pointer for the kernels that only move 16-bit patterns (either format).
 inline const __bf16* bf16_ptr(const at::Tensor& t) {
   return reinterpret_cast<const __bf16*>(t.data_ptr());
+}
+
+template <typename T>
+inline const T* ptr16(const at::Tensor& t) {
+  return reinterpret_cast<const T*>(t.data_ptr());
 }
 
 }  // namespace
 
 at::Tensor conv_build_wT(at::Tensor w) {
-  check_nhwc_bf16(w, "w");
+  check_nhwc_16(w, "w");
   const int K = w.size(0), C = w.size(1), R = w.size(2), S = w.size(3);
   auto wT = at::empty({C, R, S, K}, w.options().memory_format(
                                         at::MemoryFormat::Contiguous));
@@ -1308,28 +1369,34 @@ at::Tensor conv_build_wT(at::Tensor w) {
 
 namespace {
 // One WTList entry: src (K,C,R,S) channels_last -> wT (C,R,S,K) contiguous,
-// with an optional bf16 copy of an fp32 src.
+// with an optional 16-bit copy of an fp32 src. wT, w16 and a 16-bit src share
+// one format.
 int wt_fill(WTList& tl, int t, const at::Tensor& src, const at::Tensor* w16,
             const at::Tensor& wT) {
   TORCH_CHECK(src.is_cuda() && src.dim() == 4 &&
               src.is_contiguous(at::MemoryFormat::ChannelsLast),
               "build_wT: filter must be a 4-D channels_last HIP tensor");
   const long K = src.size(0), C = src.size(1), R = src.size(2), S = src.size(3);
-  TORCH_CHECK(wT.is_cuda() && wT.scalar_type() == at::kBFloat16 &&
+  TORCH_CHECK(wT.is_cuda() && is_16bit(wT) &&
               wT.is_contiguous() && wT.dim() == 4 && wT.size(0) == C &&
               wT.size(1) == R && wT.size(2) == S && wT.size(3) == K,
-              "build_wT: wT must be a contiguous bf16 (C,R,S,K) tensor");
-  if (w16 != nullptr)
-    TORCH_CHECK(w16->is_cuda() && w16->scalar_type() == at::kBFloat16 &&
+              "build_wT: wT must be a contiguous bf16 or fp16 (C,R,S,K) tensor");
+  if (w16 != nullptr) {
+    TORCH_CHECK(w16->is_cuda() && is_16bit(*w16) &&
                 w16->sizes() == src.sizes() &&
                 w16->is_contiguous(at::MemoryFormat::ChannelsLast),
-                "build_wT: w16 must be bf16 channels_last of the filter's shape");
+                "build_wT: w16 must be bf16 or fp16, channels_last, of the "
+                "filter's shape");
+    check_same_16(*w16, "w16", wT, "wT");
+  } else {
+    check_same_16(src, "the filter", wT, "wT");
+  }
   const long nb = R * S * ((K + 63) / 64) * ((C + 63) / 64);
   TORCH_CHECK(K > 0 && C > 0 && R * S > 0 && nb < (1L << 24),
               "build_wT: filter too large");
   tl.w[t] = src.data_ptr();
-  tl.w16[t] = w16 ? reinterpret_cast<__bf16*>(w16->data_ptr()) : nullptr;
-  tl.wT[t] = reinterpret_cast<__bf16*>(wT.data_ptr());
+  tl.w16[t] = w16 ? w16->data_ptr() : nullptr;
+  tl.wT[t] = wT.data_ptr();
   tl.K[t] = (int)K; tl.C[t] = (int)C; tl.RS[t] = (int)(R * S);
   tl.nblocks[t] = (int)nb;
   return (int)nb;
@@ -1346,8 +1413,8 @@ void multi_tensor_build_wT(std::vector<at::Tensor> w16s,
     WTList tl;
     int nblocks = 0, t = 0;
     for (; t < WT_MAX_TENSORS && i < w16s.size(); ++t, ++i) {
-      TORCH_CHECK(w16s[i].scalar_type() == at::kBFloat16,
-                  "multi_tensor_build_wT expects bf16 filters");
+      TORCH_CHECK(is_16bit(w16s[i]),
+                  "multi_tensor_build_wT expects bf16 or fp16 filters");
       nblocks += wt_fill(tl, t, w16s[i], nullptr, wTs[i]);
     }
     tl.ntensors = t;
@@ -1356,15 +1423,17 @@ void multi_tensor_build_wT(std::vector<at::Tensor> w16s,
   }
 }
 
-// w16 <- bf16(w32), wT <- rotate(w16), one launch.
+// w16 <- round(w32) to w16's format, wT <- rotate(w16), one launch.
 void conv_prep_weight(at::Tensor w32, at::Tensor w16, at::Tensor wT) {
   TORCH_CHECK(w32.scalar_type() == at::kFloat,
               "conv_prep_weight expects an fp32 filter");
   WTList tl;
   const int nblocks = wt_fill(tl, 0, w32, &w16, wT);
   tl.ntensors = 1;
-  hipLaunchKernelGGL(multi_build_wT_kernel<float>, dim3(nblocks), dim3(256), 0,
-                     conv_stream(), tl);
+  auto* kern = w16.scalar_type() == at::kHalf
+      ? multi_build_wT_kernel<float, _Float16>
+      : multi_build_wT_kernel<float, __bf16>;
+  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), 0, conv_stream(), tl);
 }
 
 // tile: 0 = size heuristic, 64 or 128 = force that GEMM-M tile (the
@@ -1375,13 +1444,12 @@ inline int pick_bmt(const ConvDims& d, long tile) {
   const long tiles128 = (long)((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
   return tiles128 < 384 ? 64 : 128;  // small-M: halve tile, double blocks
 }
-}  // namespace
 
-// out (N,K,P,Q) channels_last <- x (N,C,H,W) channels_last, w (K,C,R,S)
-// channels_last (memory [K][R][S][C]).
-at::Tensor conv_fwd_igemm(at::Tensor x, at::Tensor w, long stride, long pad,
-                          long tile) {
-  check_nhwc_bf16(x, "x"); check_nhwc_bf16(w, "w");
+// The three passes are written once over the element type T; the public
+// wrappers below check the operands and pick T from their (shared) dtype.
+template <typename T>
+at::Tensor conv_fwd_igemm_t(at::Tensor x, at::Tensor w, long stride, long pad,
+                            long tile) {
   const int Nb = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int K = w.size(0), R = w.size(2), S = w.size(3);
   TORCH_CHECK(w.size(1) == C, "channel mismatch");
@@ -1413,12 +1481,12 @@ at::Tensor conv_fwd_igemm(at::Tensor x, at::Tensor w, long stride, long pad,
                Nb * P * Q, K, Kpad};
     const int bmt = pick_bmt(d, tile);
     const dim3 grid((d.N + BN - 1) / BN, (d.M + bmt - 1) / bmt);
-    auto* kern = bmt == 64 ? conv_igemm_kernel<0, false, 64, true>
-                           : conv_igemm_kernel<0, false, 128, true>;
+    auto* kern = bmt == 64 ? conv_igemm_kernel<T, 0, false, 64, true>
+                           : conv_igemm_kernel<T, 0, false, 128, true>;
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream,
-                       reinterpret_cast<const __bf16*>(x4.data_ptr()),
-                       reinterpret_cast<const __bf16*>(w4.data_ptr()),
-                       reinterpret_cast<__bf16*>(out.data_ptr()), d);
+                       ptr16<T>(x4),
+                       ptr16<T>(w4),
+                       reinterpret_cast<T*>(out.data_ptr()), d);
     return out;
   }
 
@@ -1428,29 +1496,39 @@ at::Tensor conv_fwd_igemm(at::Tensor x, at::Tensor w, long stride, long pad,
   if (tile == 228 && fast && d.N >= 96) {
     // 128x128 tile: halves the N-tile count and with it the A re-reads
     const dim3 grid((d.N + 127) / 128, (d.M + 127) / 128);
-    hipLaunchKernelGGL((conv_igemm_kernel<0, true, 128, false, 128>), grid,
-                       dim3(256), 0, stream, bf16_ptr(x), bf16_ptr(w),
-                       reinterpret_cast<__bf16*>(out.data_ptr()), d);
+    hipLaunchKernelGGL((conv_igemm_kernel<T, 0, true, 128, false, 128>), grid,
+                       dim3(256), 0, stream, ptr16<T>(x), ptr16<T>(w),
+                       reinterpret_cast<T*>(out.data_ptr()), d);
     return out;
   }
   const int bmt = pick_bmt(d, tile);
   const dim3 grid((d.N + BN - 1) / BN, (d.M + bmt - 1) / bmt);
   auto* kern = bmt == 64
-      ? (fast ? conv_igemm_kernel<0, true, 64> : conv_igemm_kernel<0, false, 64>)
-      : (fast ? conv_igemm_kernel<0, true> : conv_igemm_kernel<0, false>);
+      ? (fast ? conv_igemm_kernel<T, 0, true, 64>
+              : conv_igemm_kernel<T, 0, false, 64>)
+      : (fast ? conv_igemm_kernel<T, 0, true> : conv_igemm_kernel<T, 0, false>);
   hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream,
-                     bf16_ptr(x), bf16_ptr(w),
-                     reinterpret_cast<__bf16*>(out.data_ptr()), d);
+                     ptr16<T>(x), ptr16<T>(w),
+                     reinterpret_cast<T*>(out.data_ptr()), d);
   return out;
 }
+}  // namespace
 
-// dx (N,C,H,W) channels_last <- dy (N,K,P,Q) channels_last,
-// wT (C,R,S,K) CONTIGUOUS with taps 180°-rotated (built by the Python side).
-at::Tensor conv_dgrad_igemm(at::Tensor dy, at::Tensor wT, long H, long W,
-                            long stride, long pad, long tile) {
-  check_nhwc_bf16(dy, "dy");
-  TORCH_CHECK(wT.is_cuda() && wT.scalar_type() == at::ScalarType::BFloat16 &&
-              wT.is_contiguous(), "wT must be contiguous bf16");
+// out (N,K,P,Q) channels_last <- x (N,C,H,W) channels_last, w (K,C,R,S)
+// channels_last (memory [K][R][S][C]); bf16 or fp16, out in the same dtype.
+at::Tensor conv_fwd_igemm(at::Tensor x, at::Tensor w, long stride, long pad,
+                          long tile) {
+  check_nhwc_16(x, "x"); check_nhwc_16(w, "w");
+  check_same_16(x, "x", w, "w");
+  return x.scalar_type() == at::kHalf
+      ? conv_fwd_igemm_t<_Float16>(x, w, stride, pad, tile)
+      : conv_fwd_igemm_t<__bf16>(x, w, stride, pad, tile);
+}
+
+namespace {
+template <typename T>
+at::Tensor conv_dgrad_igemm_t(at::Tensor dy, at::Tensor wT, long H, long W,
+                              long stride, long pad, long tile) {
   const int Nb = dy.size(0), K = dy.size(1), P = dy.size(2), Q = dy.size(3);
   const int C = wT.size(0), R = wT.size(1), S = wT.size(2);
   TORCH_CHECK(wT.size(3) == K, "channel mismatch");
@@ -1478,36 +1556,53 @@ at::Tensor conv_dgrad_igemm(at::Tensor dy, at::Tensor wT, long H, long W,
     const int bmt = (tile == 64 || tile == 128) ? (int)tile
                                                 : (t128 < 384 ? 64 : 128);
     const dim3 grid((d2.N + BN - 1) / BN, (d2.M + bmt - 1) / bmt, nclass);
-    auto* kern = bmt == 64 ? conv_igemm_kernel<2, true, 64>
-                           : conv_igemm_kernel<2, true, 128>;
+    auto* kern = bmt == 64 ? conv_igemm_kernel<T, 2, true, 64>
+                           : conv_igemm_kernel<T, 2, true, 128>;
     hipLaunchKernelGGL(kern, grid, dim3(256), 0,
-                       conv_stream(), bf16_ptr(dy), bf16_ptr(wT),
-                       reinterpret_cast<__bf16*>(dx.data_ptr()), d2);
+                       conv_stream(), ptr16<T>(dy), ptr16<T>(wT),
+                       reinterpret_cast<T*>(dx.data_ptr()), d2);
     return dx;
   }
   if (tile == 228 && fast && d.N >= 96) {
     const dim3 grid((d.N + 127) / 128, (d.M + 127) / 128);
-    hipLaunchKernelGGL((conv_igemm_kernel<1, true, 128, false, 128>), grid,
-                       dim3(256), 0, conv_stream(), bf16_ptr(dy), bf16_ptr(wT),
-                       reinterpret_cast<__bf16*>(dx.data_ptr()), d);
+    hipLaunchKernelGGL((conv_igemm_kernel<T, 1, true, 128, false, 128>), grid,
+                       dim3(256), 0, conv_stream(), ptr16<T>(dy), ptr16<T>(wT),
+                       reinterpret_cast<T*>(dx.data_ptr()), d);
     return dx;
   }
   const int bmt = pick_bmt(d, tile);
   const dim3 grid((d.N + BN - 1) / BN, (d.M + bmt - 1) / bmt);
   auto* kern = bmt == 64
-      ? (fast ? conv_igemm_kernel<1, true, 64> : conv_igemm_kernel<1, false, 64>)
-      : (fast ? conv_igemm_kernel<1, true> : conv_igemm_kernel<1, false>);
+      ? (fast ? conv_igemm_kernel<T, 1, true, 64>
+              : conv_igemm_kernel<T, 1, false, 64>)
+      : (fast ? conv_igemm_kernel<T, 1, true> : conv_igemm_kernel<T, 1, false>);
   hipLaunchKernelGGL(kern, grid, dim3(256), 0, conv_stream(),
-                     bf16_ptr(dy), bf16_ptr(wT),
-                     reinterpret_cast<__bf16*>(dx.data_ptr()), d);
+                     ptr16<T>(dy), ptr16<T>(wT),
+                     reinterpret_cast<T*>(dx.data_ptr()), d);
   return dx;
 }
+}  // namespace
 
-// dw (K,C,R,S) channels_last <- dy, x; bf16, or with out_fp32 the same
-// bf16-rounded values as fp32 (the gradient of an fp32 parameter, with no
-// cast kernel between the epilogue and the optimizer). Two-stage split-K: private fp32
+// dx (N,C,H,W) channels_last <- dy (N,K,P,Q) channels_last,
+// wT (C,R,S,K) CONTIGUOUS with taps 180°-rotated (built by the Python side);
+// bf16 or fp16, dx in the same dtype.
+at::Tensor conv_dgrad_igemm(at::Tensor dy, at::Tensor wT, long H, long W,
+                            long stride, long pad, long tile) {
+  check_nhwc_16(dy, "dy");
+  TORCH_CHECK(wT.is_cuda() && is_16bit(wT) && wT.is_contiguous(),
+              "wT must be a contiguous bf16 or fp16 HIP tensor");
+  check_same_16(dy, "dy", wT, "wT");
+  return dy.scalar_type() == at::kHalf
+      ? conv_dgrad_igemm_t<_Float16>(dy, wT, H, W, stride, pad, tile)
+      : conv_dgrad_igemm_t<__bf16>(dy, wT, H, W, stride, pad, tile);
+}
+
+// dw (K,C,R,S) channels_last <- dy, x; in their 16-bit dtype, or with out_fp32
+// the same 16-bit-rounded values as fp32 (the gradient of an fp32 parameter,
+// with no cast kernel between the epilogue and the optimizer). Two-stage
+// split-K: private fp32
 // partial slabs per grid.z slice (fragment order, see store_frag_slab) + one
-// reduce pass (no atomics); splits==1 non-stem collapses to a DIRECT bf16
+// reduce pass (no atomics); splits==1 non-stem collapses to a DIRECT 16-bit
 // store. `splits`: 0 = default (~1024 blocks, plain z order: the bits this
 // path has always produced), < 0 = one resident set of blocks, > 0 = as given.
 // `wtile`: 0 = shape heuristic, 1 = v1 64x128, 2 = v2 128x128, 3 = v2 256x64
@@ -1522,24 +1617,23 @@ namespace {
 inline int wgrad_blocks_per_cu(int tile) {
   return (tile == 1 || tile == 4) ? 4 : 2;
 }
-}  // namespace
 
-at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
-                            long stride, long pad, long splits_arg,
-                            long wtile, bool out_fp32) {
-  check_nhwc_bf16(dy, "dy"); check_nhwc_bf16(x, "x");
+template <typename T>
+at::Tensor conv_wgrad_igemm_t(at::Tensor dy, at::Tensor x, long R, long S,
+                              long stride, long pad, long splits_arg,
+                              long wtile, bool out_fp32) {
   const int Nb = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int K = dy.size(1), P = dy.size(2), Q = dy.size(3);
   auto stream = conv_stream();
-  // out_fp32: same shape and strides, the bf16-rounded values widened
+  // out_fp32: same shape and strides, the 16-bit-rounded values widened
   auto dw = at::empty({K, C, R, S},
                       x.options().memory_format(at::MemoryFormat::ChannelsLast)
-                          .dtype(out_fp32 ? at::kFloat : at::kBFloat16));
+                          .dtype(out_fp32 ? at::kFloat : x.scalar_type()));
 
   const bool stem = (C == 3);
   int Cpad = C, Npad = (int)(R * S * C);
   at::Tensor x4;
-  const __bf16* xp = bf16_ptr(x);
+  const T* xp = ptr16<T>(x);
   if (stem) {
     const long npix = (long)Nb * H * W;
     x4 = at::empty({npix * 4}, x.options());
@@ -1547,7 +1641,7 @@ at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
     hipLaunchKernelGGL(pad_c3_to_c4_kernel, dim3(std::max(blocks, 1)),
                        dim3(256), 0, stream, bf16_ptr(x),
                        reinterpret_cast<__bf16*>(x4.data_ptr()), npix);
-    xp = reinterpret_cast<const __bf16*>(x4.data_ptr());
+    xp = ptr16<T>(x4);
     Cpad = 4;
     Npad = (int)(R * S * 4);
   }
@@ -1606,15 +1700,15 @@ at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
 
   if (splits == 1 && !stem && tile != 4) {
     auto* kern =
-        tile == 9 ? conv_wgrad_v2_kernel<4, 1, true, 2>
-        : tile == 8 ? conv_wgrad_v2_kernel<2, 2, true, 2>
-        : tile == 6 ? conv_wgrad_lin_kernel<4, 1, true>
-        : tile == 5 ? conv_wgrad_lin_kernel<2, 2, true>
-        : tile == 3 ? conv_wgrad_v2_kernel<4, 1, true>
-        : tile == 2 ? conv_wgrad_v2_kernel<2, 2, true>
-        : (fast ? conv_wgrad_kernel<true, false, true>
-                : conv_wgrad_kernel<false, false, true>);
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, bf16_ptr(dy), xp,
+        tile == 9 ? conv_wgrad_v2_kernel<T, 4, 1, true, 2>
+        : tile == 8 ? conv_wgrad_v2_kernel<T, 2, 2, true, 2>
+        : tile == 6 ? conv_wgrad_lin_kernel<T, 4, 1, true>
+        : tile == 5 ? conv_wgrad_lin_kernel<T, 2, 2, true>
+        : tile == 3 ? conv_wgrad_v2_kernel<T, 4, 1, true>
+        : tile == 2 ? conv_wgrad_v2_kernel<T, 2, 2, true>
+        : (fast ? conv_wgrad_kernel<T, true, false, true>
+                : conv_wgrad_kernel<T, false, false, true>);
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, ptr16<T>(dy), xp,
                        nullptr, dw.data_ptr(), d, out_fp32);
     return dw;
   }
@@ -1627,19 +1721,19 @@ at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
       ? at::zeros({MN}, x.options().dtype(at::kFloat))
       : at::empty({(long)splits * slab}, x.options().dtype(at::kFloat));
   auto* kern =
-      tile == 9 ? conv_wgrad_v2_kernel<4, 1, false, 2>
-      : tile == 8 ? conv_wgrad_v2_kernel<2, 2, false, 2>
-      : tile == 6 ? conv_wgrad_lin_kernel<4, 1, false>
-      : tile == 5 ? conv_wgrad_lin_kernel<2, 2, false>
-      : tile == 3 ? conv_wgrad_v2_kernel<4, 1, false>
-      : tile == 2 ? conv_wgrad_v2_kernel<2, 2, false>
-      : atomic ? (stem ? conv_wgrad_kernel<false, true, false, true>
-                 : fast ? conv_wgrad_kernel<true, false, false, true>
-                        : conv_wgrad_kernel<false, false, false, true>)
-      : stem ? conv_wgrad_kernel<false, true, false>
-             : (fast ? conv_wgrad_kernel<true, false, false>
-                     : conv_wgrad_kernel<false, false, false>);
-  hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, bf16_ptr(dy), xp,
+      tile == 9 ? conv_wgrad_v2_kernel<T, 4, 1, false, 2>
+      : tile == 8 ? conv_wgrad_v2_kernel<T, 2, 2, false, 2>
+      : tile == 6 ? conv_wgrad_lin_kernel<T, 4, 1, false>
+      : tile == 5 ? conv_wgrad_lin_kernel<T, 2, 2, false>
+      : tile == 3 ? conv_wgrad_v2_kernel<T, 4, 1, false>
+      : tile == 2 ? conv_wgrad_v2_kernel<T, 2, 2, false>
+      : atomic ? (stem ? conv_wgrad_kernel<T, false, true, false, true>
+                 : fast ? conv_wgrad_kernel<T, true, false, false, true>
+                        : conv_wgrad_kernel<T, false, false, false, true>)
+      : stem ? conv_wgrad_kernel<T, false, true, false>
+             : (fast ? conv_wgrad_kernel<T, true, false, false>
+                     : conv_wgrad_kernel<T, false, false, false>);
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, ptr16<T>(dy), xp,
                      part.data_ptr<float>(), nullptr, d, out_fp32);
   if (!rowmajor) {
     const int NF = TM * TN / 1024;         // f32x4 fragments per thread
@@ -1652,22 +1746,35 @@ at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
     while (!seq && zw < 16 && nslots * zw / 256 < 2L * cus && zw * 8 <= splits)
       zw *= 2;
     const int v = (seq && nslots / 256 < 2L * cus) ? 1 : 4;
-    auto* red = v == 1 ? wgrad_reduce_frag_kernel<1, 1>
-              : zw == 1 ? wgrad_reduce_frag_kernel<1, 4>
-              : zw == 2 ? wgrad_reduce_frag_kernel<2, 4>
-              : zw == 4 ? wgrad_reduce_frag_kernel<4, 4>
-              : zw == 8 ? wgrad_reduce_frag_kernel<8, 4>
-                        : wgrad_reduce_frag_kernel<16, 4>;
+    auto* red = v == 1 ? wgrad_reduce_frag_kernel<T, 1, 1>
+              : zw == 1 ? wgrad_reduce_frag_kernel<T, 1, 4>
+              : zw == 2 ? wgrad_reduce_frag_kernel<T, 2, 4>
+              : zw == 4 ? wgrad_reduce_frag_kernel<T, 4, 4>
+              : zw == 8 ? wgrad_reduce_frag_kernel<T, 8, 4>
+                        : wgrad_reduce_frag_kernel<T, 16, 4>;
     hipLaunchKernelGGL(red, dim3((unsigned)(nslots * zw * (4 / v) / 256)),
                        dim3(256), 0, stream, part.data_ptr<float>(),
                        dw.data_ptr(), out_fp32, d.M, d.N, tn, nslots, splits,
                        NF, TN / 64, (int)(R * S * C), Cpad, C);
     return dw;
   }
-  hipLaunchKernelGGL(wgrad_reduce_kernel,
+  hipLaunchKernelGGL(wgrad_reduce_kernel<T>,
                      dim3((int)std::min((MN + 255) / 256, (long)4096)),
                      dim3(256), 0, stream, part.data_ptr<float>(),
                      dw.data_ptr(), out_fp32, MN, d.N,
                      (int)(R * S * C), atomic ? 1 : splits, Cpad, C);
   return dw;
+}
+}  // namespace
+
+at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
+                            long stride, long pad, long splits_arg,
+                            long wtile, bool out_fp32) {
+  check_nhwc_16(dy, "dy"); check_nhwc_16(x, "x");
+  check_same_16(dy, "dy", x, "x");
+  return x.scalar_type() == at::kHalf
+      ? conv_wgrad_igemm_t<_Float16>(dy, x, R, S, stride, pad, splits_arg,
+                                     wtile, out_fp32)
+      : conv_wgrad_igemm_t<__bf16>(dy, x, R, S, stride, pad, splits_arg,
+                                   wtile, out_fp32);
 }

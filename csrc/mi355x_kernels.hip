@@ -770,11 +770,13 @@ __global__ void xent_bwd_kernel(const scalar_t* __restrict__ logits,
 constexpr int MT_MAX_TENSORS = 32;
 constexpr int MT_CHUNK = 1 << 13;
 
-// w16[t], where not null, is a bf16 shadow of p[t] in the same memory order
+// w16[t], where not null, is a 16-bit shadow of p[t] in the same memory order
 // (the conv layers' autocast copy of an fp32 weight): the kernel that produces
 // the new weight also stores its rounded copy, so no cast kernel runs per
-// forward. The rounding is the float -> bf16 conversion's round-to-nearest-
-// even, as in ATen's copy kernel.
+// forward. w16_half[t] gives the shadow's format, fp16 or bf16, per tensor:
+// one step may refresh both kinds. The rounding is the float -> 16-bit
+// conversion's round-to-nearest-even, as in ATen's copy kernel. The flag only
+// selects the shadow store; the update arithmetic does not see it.
 //
 // A tensor whose pointers are all 16-byte aligned (8 for w16) moves as
 // float4s; any other, and the last size % 4 elements, go element by element.
@@ -784,12 +786,14 @@ struct MTTensorList {
   float* p[MT_MAX_TENSORS];
   float* g[MT_MAX_TENSORS];
   float* m[MT_MAX_TENSORS];
-  __bf16* w16[MT_MAX_TENSORS];
+  void* w16[MT_MAX_TENSORS];
   int size[MT_MAX_TENSORS];
+  bool w16_half[MT_MAX_TENSORS];
   int ntensors;
 };
 
 typedef __attribute__((ext_vector_type(4))) __bf16 mtbf16x4;
+typedef __attribute__((ext_vector_type(4))) _Float16 mthalfx4;
 
 __global__ void multi_tensor_sgd_kernel(MTTensorList tl, float lr, float mu,
                                         float wd, bool has_momentum) {
@@ -807,7 +811,8 @@ __global__ void multi_tensor_sgd_kernel(MTTensorList tl, float lr, float mu,
   float* p = tl.p[t];
   float* g = tl.g[t];
   float* m = has_momentum ? tl.m[t] : nullptr;
-  __bf16* w16 = tl.w16[t];
+  void* w16 = tl.w16[t];
+  const bool half = tl.w16_half[t];
   const bool vec = (((size_t)p | (size_t)g | (size_t)m) & 15) == 0 &&
                    ((size_t)w16 & 7) == 0;
   int tail = start;   // first element of the scalar loop
@@ -831,10 +836,17 @@ __global__ void multi_tensor_sgd_kernel(MTTensorList tl, float lr, float mu,
       if (has_momentum) *(float4*)(m + i) = *(float4*)mv;
       *(float4*)(p + i) = *(float4*)pv;
       if (w16 != nullptr) {
-        mtbf16x4 o;
-        #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (__bf16)pv[e];
-        *(mtbf16x4*)(w16 + i) = o;
+        if (half) {
+          mthalfx4 o;
+          #pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = (_Float16)pv[e];
+          *(mthalfx4*)((_Float16*)w16 + i) = o;
+        } else {
+          mtbf16x4 o;
+          #pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = (__bf16)pv[e];
+          *(mtbf16x4*)((__bf16*)w16 + i) = o;
+        }
       }
     }
   }
@@ -846,7 +858,10 @@ __global__ void multi_tensor_sgd_kernel(MTTensorList tl, float lr, float mu,
     }
     const float pn = p[i] - lr * grad;
     p[i] = pn;
-    if (w16 != nullptr) w16[i] = (__bf16)pn;
+    if (w16 != nullptr) {
+      if (half) ((_Float16*)w16)[i] = (_Float16)pn;
+      else ((__bf16*)w16)[i] = (__bf16)pn;
+    }
   }
 }
 
@@ -1824,12 +1839,17 @@ void multi_tensor_sgd(std::vector<at::Tensor> params,
       tl.g[t] = grads[i].data_ptr<float>();
       tl.m[t] = has_momentum ? bufs[i].data_ptr<float>() : nullptr;
       tl.w16[t] = nullptr;
+      tl.w16_half[t] = false;
       if (!w16s.empty() && w16s[i].has_value()) {
         const at::Tensor& w16 = *w16s[i];
-        TORCH_CHECK(w16.is_cuda() && w16.scalar_type() == at::kBFloat16 &&
+        TORCH_CHECK(w16.is_cuda() &&
+                    (w16.scalar_type() == at::kBFloat16 ||
+                     w16.scalar_type() == at::kHalf) &&
                     w16.sizes() == p.sizes() && w16.strides() == p.strides(),
-                    "multi_tensor_sgd: w16 must be bf16 in the param's layout");
-        tl.w16[t] = reinterpret_cast<__bf16*>(w16.data_ptr());
+                    "multi_tensor_sgd: w16 must be bf16 or fp16 in the "
+                    "param's layout");
+        tl.w16[t] = w16.data_ptr();
+        tl.w16_half[t] = w16.scalar_type() == at::kHalf;
       }
       tl.size[t] = (int)p.numel();
       nblocks += (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
@@ -2017,7 +2037,7 @@ at::Tensor class_rank(at::Tensor logits, at::Tensor target) {
   return rank;
 }
 
-// csrc/conv_igemm.hip — implicit-GEMM MFMA convolution (NHWC bf16)
+// csrc/conv_igemm.hip — implicit-GEMM MFMA convolution (NHWC bf16 or fp16)
 at::Tensor conv_build_wT(at::Tensor w);
 at::Tensor conv_fwd_igemm(at::Tensor x, at::Tensor w, long stride, long pad,
                           long tile);
@@ -2040,17 +2060,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_build_wT", &conv_build_wT,
         "build rotated/transposed filter for dgrad (one launch)");
   m.def("conv_fwd_igemm", &conv_fwd_igemm,
-        "implicit-GEMM conv forward (NHWC bf16, MFMA); tile 0=auto|64|128",
+        "implicit-GEMM conv forward (NHWC bf16|fp16, MFMA); tile 0=auto|64|128",
         py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad"),
         py::arg("tile") = 0);
   m.def("conv_dgrad_igemm", &conv_dgrad_igemm,
-        "implicit-GEMM conv input-grad (NHWC bf16, MFMA); tile 0=auto|64|128",
+        "implicit-GEMM conv input-grad (NHWC bf16|fp16, MFMA); "
+        "tile 0=auto|64|128",
         py::arg("dy"), py::arg("wT"), py::arg("H"), py::arg("W"),
         py::arg("stride"), py::arg("pad"), py::arg("tile") = 0);
   m.def("conv_wgrad_igemm", &conv_wgrad_igemm,
-        "implicit-GEMM conv weight-grad -> bf16 channels_last (K,C,R,S); "
+        "implicit-GEMM conv weight-grad -> channels_last (K,C,R,S) in the "
+        "input dtype; "
         "two-stage split-K, no atomics; splits 0=auto; wtile 0=auto, "
-        "1=64x128, 2=128x128, 3=256x64; out_fp32: the same bf16-rounded "
+        "1=64x128, 2=128x128, 3=256x64; out_fp32: the same 16-bit-rounded "
         "values as an fp32 tensor",
         py::arg("dy"), py::arg("x"), py::arg("R"), py::arg("S"),
         py::arg("stride"), py::arg("pad"), py::arg("splits") = 0,
@@ -2058,7 +2080,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("multi_tensor_build_wT", &multi_tensor_build_wT,
         "wT[i] <- rotated/transposed w16[i] for every filter, one launch");
   m.def("conv_prep_weight", &conv_prep_weight,
-        "w16 <- bf16(w32) and wT <- rotated/transposed w16, one launch");
+        "w16 <- w32 rounded to w16.dtype (bf16|fp16) and wT <- "
+        "rotated/transposed w16, one launch");
   m.def("bn_stats", &bn_stats, "per-channel sum/sqsum (NCHW)");
   m.def("bn_stats_packed", &bn_stats_packed,
         "per-channel {sum,sqsum} packed [2C], no-atomic NHWC v2");
@@ -2087,7 +2110,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xent_fwd", &xent_fwd, "fused softmax cross-entropy forward");
   m.def("xent_bwd", &xent_bwd, "fused softmax cross-entropy backward");
   m.def("multi_tensor_sgd", &multi_tensor_sgd,
-        "fused multi-tensor SGD step; w16s: per-param bf16 shadow (or None) "
+        "fused multi-tensor SGD step; w16s: per-param bf16|fp16 shadow (or "
+        "None) "
         "that receives the rounded new weight",
         py::arg("params"), py::arg("grads"), py::arg("bufs"), py::arg("lr"),
         py::arg("momentum"), py::arg("weight_decay"),

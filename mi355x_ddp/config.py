@@ -115,7 +115,13 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                             "resnet152", "resnet18_imagenet",
                             "resnet50_imagenet"])
     p.add_argument("--amp", default=None, type=str,
-                   choices=[None, "fp32", "bf16", "fp16", "bf16_o2"])
+                   choices=[None, "fp32", "bf16", "fp16", "bf16_o2"],
+                   help="precision. fp32: convs on MIOpen. bf16: autocast, "
+                        "convs on the native bf16 MFMA kernels. fp16: "
+                        "autocast + dynamic loss scaler, convs on the native "
+                        "fp16 MFMA kernels (MI355X_NATIVE_CONV_FP16=0 sends "
+                        "them to MIOpen). bf16_o2: bf16 model with fp32 "
+                        "masters, native bf16 convs")
     p.add_argument("--no-sync-bn", action="store_true")
     p.add_argument("--num_workers", default=4, type=int)
     p.add_argument("--log_interval", default=10, type=int)

@@ -1,12 +1,15 @@
-"""Native implicit-GEMM convolution (NHWC bf16, MFMA) with torch fallback.
+"""Native implicit-GEMM convolution (NHWC bf16 or fp16, MFMA) with torch
+fallback.
 
 MI355X-native replacement for the reference's cuDNN conv dependency
 (every nn.Conv2d in reference utils/model.py — 3x3 s1/s2
 and 1x1 convs of the CIFAR ResNet). The HIP kernels (csrc/conv_igemm.hip)
-run when the tensor is a bf16 channels_last CUDA tensor; anything else
-(CPU tests, fp32 mode, exotic shapes) runs torch's conv so the same module
-is testable everywhere. ``MI355X_NATIVE_CONV=0`` forces the torch path for
-parity A/B.
+run when input and weight are channels_last CUDA tensors of one 16-bit
+dtype, bf16 or fp16 (``--amp bf16`` / ``--amp fp16``: the autocast dtype);
+anything else (CPU tests, fp32 mode, exotic shapes) runs torch's conv so the
+same module is testable everywhere. ``MI355X_NATIVE_CONV=0`` forces the torch
+path for parity A/B; ``MI355X_NATIVE_CONV_FP16=0`` does so for fp16 only
+(bf16 keeps the native kernels): the A/B switch for the fp16 kernels.
 
 Autotune (the ``cudnn.benchmark=True`` equivalent the reference relies on,
 distributed.py:48): per conv shape, the GEMM-M tile (64 vs 128) for
@@ -14,9 +17,11 @@ fwd/dgrad and the split-K factor for wgrad are measured once at first use
 with hip events and cached for the rest of the process. ``MI355X_AUTOTUNE=0``
 falls back to the static size heuristic inside the kernels.
 
-Weight shadows. Under bf16 autocast an fp32 conv weight is needed in two
-other forms: its bf16 copy (forward, wgrad) and the 180-degree-rotated
-transposed bf16 filter (dgrad). Both change only when the weight changes,
+Weight shadows. Under 16-bit autocast an fp32 conv weight is needed in two
+other forms: its copy in the autocast dtype (forward, wgrad) and the
+180-degree-rotated transposed filter in that dtype (dgrad). A shadow records
+its dtype; a weight used under the other 16-bit dtype gets a new shadow.
+Both forms change only when the weight changes,
 i.e. once per optimizer step, so ``MI355Conv2d`` keeps them as persistent
 tensors (``WeightShadow``: ``w16``, ``wT``) instead of casting per forward
 and rotating per backward. ``FusedSGD`` rewrites them in the step that
@@ -25,7 +30,7 @@ produces the new weight; any other writer is caught at the next forward by a
 ``conv_prep_weight`` launch. A writer the version counter cannot see
 (``p.data.<op>_()``, raw-pointer kernels) MUST call
 ``invalidate_weight_shadows``. The weight gradient comes back from the wgrad
-epilogue as fp32 (the bf16-rounded value, widened), so autograd inserts no
+epilogue as fp32 (the 16-bit-rounded value, widened), so autograd inserts no
 cast node in either direction and results are bit-equal to the cast path.
 ``MI355X_WEIGHT_SHADOWS=0`` restores the per-call casts (A/B switch);
 ``MI355X_CHECK_SHADOWS=1`` verifies the shadows against a fresh cast and
@@ -47,6 +52,13 @@ def native_conv_wanted() -> bool:
     return os.environ.get("MI355X_NATIVE_CONV", "1") == "1"
 
 
+def native_conv_fp16_wanted() -> bool:
+    return os.environ.get("MI355X_NATIVE_CONV_FP16", "1") == "1"
+
+
+_NATIVE_DTYPES = (torch.bfloat16, torch.float16)
+
+
 def autotune_wanted() -> bool:
     return os.environ.get("MI355X_AUTOTUNE", "1") == "1"
 
@@ -62,12 +74,15 @@ def check_shadows_wanted() -> bool:
 def _native_ok(x: torch.Tensor, weight: torch.Tensor, stride, padding,
                dilation, groups, weight_dtype=None) -> bool:
     """`weight_dtype` overrides weight.dtype: the dtype the kernels will see
-    when a bf16 shadow stands in for an fp32 weight."""
+    when a 16-bit shadow stands in for an fp32 weight. x and weight must
+    share one 16-bit dtype, bf16 or fp16."""
     if not native_conv_wanted() or not _backend.native_enabled(x):
         return False
     if weight_dtype is None:
         weight_dtype = weight.dtype
-    if x.dtype != torch.bfloat16 or weight_dtype != torch.bfloat16:
+    if x.dtype not in _NATIVE_DTYPES or weight_dtype != x.dtype:
+        return False
+    if x.dtype == torch.float16 and not native_conv_fp16_wanted():
         return False
     if groups != 1 or dilation[0] != 1 or dilation[1] != 1:
         return False
@@ -141,6 +156,12 @@ def _tuned_choice(key: Tuple, candidates: Sequence,
     return best
 
 
+def _tune_key(kind: str, dtype: torch.dtype, *shape) -> Tuple:
+    """Cache key of one pass: the operands' dtype comes right after the pass
+    name, so bf16 and fp16 runs of one shape are tuned separately."""
+    return (kind, dtype) + tuple(shape)
+
+
 def clear_autotune_cache() -> None:
     _TUNE_CACHE.clear()
 
@@ -152,7 +173,12 @@ def tune_report() -> str:
     for key in sorted(_TUNE_CACHE, key=str):
         choice = _TUNE_CACHE[key]
         label = "MIOpen" if choice == MIOPEN else str(choice)
-        lines.append(f"{key[0]:>12} {str(key[1:]):<70} -> {label}")
+        # _ConvIGEMM's keys carry the dtype of the pass's operands at [1]
+        if len(key) > 1 and isinstance(key[1], torch.dtype):
+            dt, rest = str(key[1]).replace("torch.", ""), key[2:]
+        else:
+            dt, rest = "", key[1:]
+        lines.append(f"{key[0]:>12} {dt:>8} {str(rest):<70} -> {label}")
     return "\n".join(lines) if lines else "(autotune cache empty)"
 
 
@@ -171,18 +197,23 @@ def rotate_wT(w16: torch.Tensor) -> torch.Tensor:
 
 class WeightShadow:
     """`w16` (the weight's shape and strides) and `wT` ((C,R,S,K) contiguous)
-    of one fp32 (K,C,R,S) weight. Both are allocated once and only ever
+    of one fp32 (K,C,R,S) weight, both in `dtype` (bf16 or fp16: the autocast
+    dtype the weight is used under). Both are allocated once and only ever
     rewritten in place, so a hipGraph-captured step that reads or writes them
     stays replayable. `stamp` is (weight._version, weight.data_ptr()) at the
     time they were last written, None when known stale."""
 
-    __slots__ = ("w16", "wT", "stamp", "refreshes")
+    __slots__ = ("w16", "wT", "dtype", "stamp", "refreshes")
 
-    def __init__(self, weight: torch.Tensor):
+    def __init__(self, weight: torch.Tensor,
+                 dtype: torch.dtype = torch.bfloat16):
+        if dtype not in _NATIVE_DTYPES:
+            raise ValueError(f"a weight shadow is bf16 or fp16, not {dtype}")
         K, C, R, S = weight.shape
+        self.dtype = dtype
         # empty_like keeps the strides of a dense tensor
-        self.w16 = torch.empty_like(weight.detach(), dtype=torch.bfloat16)
-        self.wT = torch.empty((C, R, S, K), dtype=torch.bfloat16,
+        self.w16 = torch.empty_like(weight.detach(), dtype=dtype)
+        self.wT = torch.empty((C, R, S, K), dtype=dtype,
                               device=weight.device)
         self.stamp = None
         self.refreshes = 0
@@ -221,10 +252,10 @@ class WeightShadow:
 
     def check(self, weight: torch.Tensor) -> None:
         """Raise if the shadows differ from a fresh cast + rotate."""
-        w16 = weight.detach().to(torch.bfloat16)
+        w16 = weight.detach().to(self.dtype)
         if not torch.equal(self.w16, w16):
-            raise RuntimeError("stale bf16 weight shadow (w16) for a weight "
-                               f"of shape {tuple(weight.shape)}")
+            raise RuntimeError(f"stale {self.dtype} weight shadow (w16) for a "
+                               f"weight of shape {tuple(weight.shape)}")
         if not torch.equal(self.wT, rotate_wT(w16)):
             raise RuntimeError("stale rotated weight shadow (wT) for a weight "
                                f"of shape {tuple(weight.shape)}")
@@ -235,11 +266,14 @@ def shadow_of(weight: torch.Tensor) -> Optional[WeightShadow]:
     return getattr(weight, "_mi355x_shadow", None)
 
 
-def _shadow_for(weight: torch.Tensor) -> WeightShadow:
-    """Fresh shadow of `weight`, created at first use."""
+def _shadow_for(weight: torch.Tensor,
+                dtype: torch.dtype = torch.bfloat16) -> WeightShadow:
+    """Fresh shadow of `weight` in `dtype`, created at first use; a shadow of
+    the other 16-bit dtype (the model ran under the other autocast mode
+    before) is replaced."""
     sh = shadow_of(weight)
-    if sh is None or not sh.matches(weight):
-        sh = WeightShadow(weight)
+    if sh is None or sh.dtype != dtype or not sh.matches(weight):
+        sh = WeightShadow(weight, dtype)
         weight._mi355x_shadow = sh
     sh.ensure(weight)
     if check_shadows_wanted():
@@ -296,7 +330,10 @@ class _ConvIGEMM(torch.autograd.Function):
                 return F.conv2d(x, weight, None, stride, padding)
             return C.conv_fwd_igemm(x, weight, stride, padding, t)
 
-        key = ("fwd", x.shape, weight.shape, stride, padding)
+        # the dtype is part of every key: a choice measured for bf16 is never
+        # replayed for fp16 in the same process
+        key = _tune_key("fwd", x.dtype, x.shape, weight.shape, stride,
+                        padding)
         return run(_tuned_choice(key, (64, 128, 228, MIOPEN), run, default=0))
 
     @staticmethod
@@ -321,7 +358,8 @@ class _ConvIGEMM(torch.autograd.Function):
                 return C.conv_dgrad_igemm(dy, wT, x.shape[2], x.shape[3],
                                           ctx.stride, ctx.padding, t)
 
-            key = ("dgrad", dy.shape, wT.shape, ctx.stride, ctx.padding)
+            key = _tune_key("dgrad", x.dtype, dy.shape, wT.shape,
+                            ctx.stride, ctx.padding)
             dx = run_dx(_tuned_choice(key, (64, 128, 228, MIOPEN), run_dx,
                                       default=0))
         if ctx.needs_input_grad[1]:
@@ -345,7 +383,8 @@ class _ConvIGEMM(torch.autograd.Function):
 
             # two-phase: pick the tile (v1/v2 variants vs MIOpen), then the
             # split-K factor for the winning native tile
-            kt = ("wgrad_tile", dy.shape, x.shape, R, ctx.stride, ctx.padding)
+            kt = _tune_key("wgrad_tile", x.dtype, dy.shape, x.shape, R,
+                           ctx.stride, ctx.padding)
             tile = _tuned_choice(
                 kt, ((0, 0), (1, -1), (2, -1), (3, -1), (4, 0), (5, -1),
                      (6, -1), MIOPEN),
@@ -353,8 +392,8 @@ class _ConvIGEMM(torch.autograd.Function):
             if tile == MIOPEN:
                 choice = MIOPEN
             else:
-                ks = ("wgrad_splits", dy.shape, x.shape, R, ctx.stride,
-                      ctx.padding, tile[0])
+                ks = _tune_key("wgrad_splits", x.dtype, dy.shape, x.shape,
+                               R, ctx.stride, ctx.padding, tile[0])
                 # 0 = the kernel's default (~1024 blocks, the bit-stable
                 # count), -1 = one resident set of blocks (3..200 slices on
                 # the ResNet shapes); the explicit counts bracket both
@@ -375,25 +414,31 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, stride=(1, 1),
 class MI355Conv2d(nn.Conv2d):
     """nn.Conv2d whose hot path is the implicit-GEMM HIP kernel.
 
-    Under bf16 autocast the input is cast explicitly (custom autograd
-    Functions are invisible to autocast's casting). An fp32 channels_last
-    weight headed for the native kernels is not cast per call: its
-    WeightShadow (see the module docstring) supplies the bf16 and rotated
-    forms. Every other fp32 weight is cast per call as before, and a weight
-    that already is bf16 (`bf16_o2`) needs neither. Outside autocast the
-    native path runs only when the tensors already are bf16.
+    Under bf16 or fp16 autocast the input is cast explicitly to the autocast
+    dtype (custom autograd Functions are invisible to autocast's casting). An
+    fp32 channels_last weight headed for the native kernels is not cast per
+    call: its WeightShadow (see the module docstring) supplies the 16-bit and
+    rotated forms in that dtype. Every other fp32 weight is cast per call as
+    before, and a weight that already is bf16 (`bf16_o2`) needs neither.
+    Outside autocast the native path runs only when the tensors already share
+    one 16-bit dtype.
     """
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         weight = self.weight
-        if torch.is_autocast_enabled() and \
-                torch.get_autocast_dtype("cuda") == torch.bfloat16 and x.is_cuda:
-            x = x.to(torch.bfloat16)
+        dt = torch.get_autocast_dtype("cuda") \
+            if torch.is_autocast_enabled() and x.is_cuda else None
+        # MI355X_NATIVE_CONV_FP16=0: fp16 autocast is left to torch's conv,
+        # casts included, as before the fp16 kernels existed
+        if dt == torch.float16 and not native_conv_fp16_wanted():
+            dt = None
+        if dt in _NATIVE_DTYPES:
+            x = x.to(dt)
             if self._shadow_ok(x, weight):
-                sh = _shadow_for(weight)
+                sh = _shadow_for(weight, dt)
                 return _ConvIGEMM.apply(x, weight, self.stride[0],
                                         self.padding[0], sh.w16, sh.wT)
-            weight = weight.to(torch.bfloat16)
+            weight = weight.to(dt)
         return conv2d(x, weight, self.stride, self.padding, self.dilation,
                       self.groups)
 
@@ -404,7 +449,7 @@ class MI355Conv2d(nn.Conv2d):
                 weight.is_contiguous(memory_format=torch.channels_last) and
                 _native_ok(x, weight, self.stride, self.padding,
                            self.dilation, self.groups,
-                           weight_dtype=torch.bfloat16))
+                           weight_dtype=x.dtype))
 
     @classmethod
     def convert(cls, module: nn.Module) -> nn.Module:

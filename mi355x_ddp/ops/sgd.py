@@ -18,14 +18,15 @@ the master and the bf16 parameter is its rounded copy —
 
 Mixed models (some fp32, some bf16 tensors) split into the two paths.
 
-Conv weight shadows (ops/conv.py): an fp32 conv weight used under bf16
-autocast carries persistent bf16 (`w16`) and rotated (`wT`) copies. The
-native kernels here write parameters through raw pointers, which the
-tensor's version counter does not see, so for every parameter it updates
-that carries a shadow the step either rewrites the shadow itself — the SGD
-kernel stores bf16(p_new) into `w16` next to `p`, and one batched
-`multi_tensor_build_wT` launch rotates every `w16` into its `wT` — or marks
-it stale. Never neither.
+Conv weight shadows (ops/conv.py): an fp32 conv weight used under 16-bit
+autocast carries persistent copies in the autocast dtype, bf16 or fp16:
+`w16` and the rotated `wT`. The native kernels here write parameters through
+raw pointers, which the tensor's version counter does not see, so for every
+parameter it updates that carries a shadow the step either rewrites the
+shadow itself — the SGD kernel stores p_new rounded to the shadow's dtype
+into `w16` next to `p` (per tensor: one step may carry bf16 and fp16
+shadows), and one batched `multi_tensor_build_wT` launch rotates every `w16`
+into its `wT` — or marks it stale. Never neither.
 """
 from __future__ import annotations
 

@@ -2,7 +2,8 @@
 """Per-shape micro-benchmark: native implicit-GEMM conv vs MIOpen (F.conv2d).
 
 Times fwd / dgrad / wgrad for every conv shape of a model config at the bench
-batch size, bf16 channels_last, and prints a table with speedups. Run on an
+batch size, channels_last in bf16 or fp16 (--dtype), and prints a table with
+speedups. Run on an
 MI355X box; output goes to stdout (redirect into gpurun_out/).
 
 Default: the ResNet18 CIFAR table (round-1 baseline format). --arch/--image-
@@ -81,9 +82,14 @@ def main():
     p.add_argument("--image-size", type=int, default=32)
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16",
+                   help="16-bit format of the operands, for the native "
+                        "kernels and the MIOpen column alike")
     args = p.parse_args()
     from mi355x_ddp import _C
 
+    dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
+    print(f"# dtype {args.dtype}, batch {args.batch}")
     N = args.batch
     if args.arch:
         rows = collect_model_shapes(args.arch, args.image_size)
@@ -95,9 +101,9 @@ def main():
           f"{'igemm us':>9} {'best us':>9} {'cfg':>9} {'x':>6} {'TF/s':>7}")
     tot_m = tot_i = tot_b = 0.0  # weighted by multiplicity
     for name, c, h, w, k, r, stride, pad, cnt in rows:
-        x = torch.randn(N, c, h, w, device="cuda", dtype=torch.bfloat16) \
+        x = torch.randn(N, c, h, w, device="cuda", dtype=dtype) \
             .to(memory_format=torch.channels_last)
-        wt = (torch.randn(k, c, r, r, device="cuda", dtype=torch.bfloat16)
+        wt = (torch.randn(k, c, r, r, device="cuda", dtype=dtype)
               / (c * r * r) ** 0.5).to(memory_format=torch.channels_last)
         ph = ((h + 2 * pad - r) // stride + 1)
         pw = ((w + 2 * pad - r) // stride + 1)
