@@ -21,6 +21,12 @@
 //
 // SCALAR path (NCHW output, odd sizes): one output element per thread,
 // coalesced stores, table and bytes read through L2.
+//
+// CutMix (batch_augment_cutmix, further down): the same two paths with a
+// partner image per sample, given as a DATASET index, whose pixels replace the
+// sample's inside a box. The fast path stages the partner into a second LDS
+// region, for mixed rows only, and applies while table + two images fit 64 KB
+// of LDS; the source is chosen per pixel and is still one byte per element.
 #include <torch/extension.h>
 #include <ATen/ATen.h>
 #include <hip/hip_runtime.h>
@@ -37,6 +43,9 @@ constexpr int LUT_N = 3 * 256;
 // LDS budget of the fast path: image bytes + table; larger images take the
 // scalar path
 constexpr long FAST_MAX_IMG_BYTES = 48 * 1024;
+// CutMix fast path: table + two images within the 64 KB of dynamic LDS a
+// launch gets without raising the kernel's attribute
+constexpr long CUTMIX_FAST_MAX_LDS = 64 * 1024;
 
 // fp32 -> output element, round to nearest even. The table holds finite
 // values only, so the bf16 bit trick needs no NaN case.
@@ -228,12 +237,221 @@ void launch_batch_augment(const at::Tensor& images, const at::Tensor& labels,
   }
 }
 
+// ---- CutMix --------------------------------------------------------------
+// mix[i] = (partner dataset index or -1, y0 | y1 << 16, x0 | x1 << 16) and
+// lam[i], both indexed by DATASET index like aug. Inside the box (output
+// coordinates, exclusive ends) the pixel is the partner's, with the partner's
+// own crop and flip; everywhere else it is the sample's. Still one byte looked
+// up in the table per element, so still no float arithmetic.
+struct MixParams { int partner, y0, y1, x0, x1; };
+
+// A partner outside [0, M) is "not mixed" and comes back as -1.
+__device__ __forceinline__ MixParams load_mix(const int* __restrict__ mix,
+                                              int i, int M) {
+  MixParams q;
+  const int p = mix[3 * (long)i], ys = mix[3 * (long)i + 1],
+            xs = mix[3 * (long)i + 2];
+  q.partner = (unsigned)p < (unsigned)M ? p : -1;
+  q.y0 = ys & 0xffff; q.y1 = (ys >> 16) & 0xffff;
+  q.x0 = xs & 0xffff; q.x1 = (xs >> 16) & 0xffff;
+  return q;
+}
+
+__device__ __forceinline__ bool in_box(int h, int w, const MixParams& q) {
+  return h >= q.y0 && h < q.y1 && w >= q.x0 && w < q.x1;
+}
+
+// Fast path: batch_augment_nhwc_kernel with a second LDS image, staged only
+// when the row is mixed (block-uniform). src2_off is the partner image's
+// offset from s_img (a multiple of 16), so one LDS base serves both sources.
+template <typename T>
+__global__ __launch_bounds__(AUG_THREADS)
+void batch_augment_cutmix_nhwc_kernel(const unsigned char* __restrict__ images,
+                                      const long* __restrict__ labels,
+                                      const int* __restrict__ idx,
+                                      const int* __restrict__ aug,
+                                      const int* __restrict__ mix,
+                                      const float* __restrict__ lam,
+                                      const float* __restrict__ lut,
+                                      T* __restrict__ out,
+                                      long* __restrict__ labels_a_out,
+                                      long* __restrict__ labels_b_out,
+                                      float* __restrict__ lam_out,
+                                      int M, int H, int W, int pad,
+                                      int wide_src, int src2_off) {
+  constexpr int VEC = 16 / (int)sizeof(T);
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  T* s_lut = reinterpret_cast<T*>(smem);                  // [3][256], rounded
+  unsigned char* s_img = smem + LUT_N * sizeof(T);        // 2 x [H][W][3]
+
+  const int n = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int img_bytes = H * W * 3;
+  const int i = idx[n];
+  const bool in_range = (unsigned)i < (unsigned)M;
+  MixParams q;
+  q.partner = -1; q.y0 = q.y1 = q.x0 = q.x1 = 0;
+  if (in_range) q = load_mix(mix, i, M);
+  const bool mixed = q.partner >= 0;
+
+  for (int e = tid; e < LUT_N; e += AUG_THREADS)
+    s_lut[e] = OutCvt<T>::cvt(lut[e]);
+  // which = 0: the sample into s_img; which = 1: the partner behind it
+  for (int which = 0; which < 2; ++which) {
+    if (which == 0 ? !in_range : !mixed) continue;
+    const unsigned char* src =
+        images + (long)(which == 0 ? i : q.partner) * img_bytes;
+    unsigned char* dstb = s_img + (which == 0 ? 0 : src2_off);
+    if (wide_src) {
+      const uint4* src4 = reinterpret_cast<const uint4*>(src);
+      uint4* dst4 = reinterpret_cast<uint4*>(dstb);
+      for (int e = tid; e < img_bytes / 16; e += AUG_THREADS)
+        dst4[e] = src4[e];
+    } else {
+      for (int e = tid; e < img_bytes; e += AUG_THREADS) dstb[e] = src[e];
+    }
+  }
+  if (tid == 0) {
+    const long la = in_range ? labels[i] : -1L;
+    labels_a_out[n] = la;
+    labels_b_out[n] = mixed ? labels[q.partner] : la;
+    lam_out[n] = mixed ? lam[i] : 1.0f;
+  }
+  const AugParams p = load_aug(aug, in_range ? i : 0, pad);
+  const AugParams pp = load_aug(aug, mixed ? q.partner : 0, pad);
+  __syncthreads();
+
+  // LDS offset of the source byte of output (h, w), channel 0, or -1
+  auto source = [&](int h, int w) -> int {
+    if (!in_range) return -1;
+    if (mixed && in_box(h, w, q)) {
+      const int so = src_pixel(h, w, H, W, pp, pad);
+      return so < 0 ? -1 : so + src2_off;
+    }
+    return src_pixel(h, w, H, W, p, pad);
+  };
+
+  T* dst = out + (long)n * img_bytes;
+  for (int chunk = tid; chunk < img_bytes / VEC; chunk += AUG_THREADS) {
+    const int e0 = chunk * VEC;
+    int pix = e0 / 3;
+    int c = e0 - pix * 3;
+    int h = pix / W;
+    int w = pix - h * W;
+    int so = source(h, w);
+    __attribute__((aligned(16))) T v[VEC];
+    #pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      const int byte = so < 0 ? 0 : (int)s_img[so + c];
+      v[j] = s_lut[c * 256 + byte];
+      if (++c == 3) {
+        c = 0;
+        if (++w == W) { w = 0; ++h; }
+        // as in batch_augment_nhwc_kernel: computed for h == H after the
+        // image's last element, never used
+        so = source(h, w);
+      }
+    }
+    *reinterpret_cast<uint4*>(dst + e0) = *reinterpret_cast<const uint4*>(v);
+  }
+}
+
+// Scalar path: batch_augment_scalar_kernel with the source chosen per element.
+template <typename T>
+__global__ __launch_bounds__(AUG_THREADS)
+void batch_augment_cutmix_scalar_kernel(
+    const unsigned char* __restrict__ images, const long* __restrict__ labels,
+    const int* __restrict__ idx, const int* __restrict__ aug,
+    const int* __restrict__ mix, const float* __restrict__ lam,
+    const float* __restrict__ lut, T* __restrict__ out,
+    long* __restrict__ labels_a_out, long* __restrict__ labels_b_out,
+    float* __restrict__ lam_out, int N, int M, int H, int W, int pad,
+    int channels_last) {
+  const int HW = H * W;
+  const long per_img = (long)HW * 3;
+  const long total = (long)N * per_img;
+  const long stride = (long)gridDim.x * AUG_THREADS;
+  for (long t = (long)blockIdx.x * AUG_THREADS + threadIdx.x; t < total;
+       t += stride) {
+    const int n = (int)(t / per_img);
+    const int r = (int)(t - (long)n * per_img);
+    int c, pix;
+    if (channels_last) { pix = r / 3; c = r - pix * 3; }
+    else               { c = r / HW;  pix = r - c * HW; }
+    const int h = pix / W, w = pix - h * W;
+    const int i = idx[n];
+    int byte = 0;
+    if ((unsigned)i < (unsigned)M) {
+      const MixParams q = load_mix(mix, i, M);
+      const int k = q.partner >= 0 && in_box(h, w, q) ? q.partner : i;
+      const AugParams p = load_aug(aug, k, pad);
+      const int so = src_pixel(h, w, H, W, p, pad);
+      if (so >= 0) byte = images[(long)k * per_img + so + c];
+    }
+    out[t] = OutCvt<T>::cvt(lut[c * 256 + byte]);
+    if (t < N) {
+      const int il = idx[t];
+      long la = -1L, lb = -1L;
+      float lm = 1.0f;
+      if ((unsigned)il < (unsigned)M) {
+        const MixParams q = load_mix(mix, il, M);
+        la = labels[il];
+        lb = q.partner >= 0 ? labels[q.partner] : la;
+        if (q.partner >= 0) lm = lam[il];
+      }
+      labels_a_out[t] = la;
+      labels_b_out[t] = lb;
+      lam_out[t] = lm;
+    }
+  }
+}
+
+template <typename T>
+void launch_batch_augment_cutmix(const unsigned char* img, const long* labels,
+                                 const int* idx, const int* aug,
+                                 const int* mix, const float* lam,
+                                 const float* lut, void* out,
+                                 long* labels_a_out, long* labels_b_out,
+                                 float* lam_out, int N, int M, int H, int W,
+                                 int pad, bool channels_last,
+                                 hipStream_t stream) {
+  const long img_bytes = (long)H * W * 3;
+  // the partner image starts at the next 16-byte boundary behind the sample
+  const long src2_off = (img_bytes + 15) / 16 * 16;
+  const long smem = (long)(LUT_N * sizeof(T)) + src2_off + img_bytes;
+  const bool fast = channels_last &&
+      (img_bytes * (long)sizeof(T)) % 16 == 0 &&
+      smem <= CUTMIX_FAST_MAX_LDS;
+  if (fast) {
+    const int wide_src = img_bytes % 16 == 0 &&
+        reinterpret_cast<uintptr_t>(img) % 16 == 0;
+    hipLaunchKernelGGL(batch_augment_cutmix_nhwc_kernel<T>, dim3(N),
+                       dim3(AUG_THREADS), (size_t)smem, stream, img, labels,
+                       idx, aug, mix, lam, lut, static_cast<T*>(out),
+                       labels_a_out, labels_b_out, lam_out, M, H, W, pad,
+                       wide_src, (int)src2_off);
+  } else {
+    const long total = (long)N * img_bytes;
+    const int blocks = (int)std::min((total + AUG_THREADS - 1) / AUG_THREADS,
+                                     (long)65536);
+    hipLaunchKernelGGL(batch_augment_cutmix_scalar_kernel<T>, dim3(blocks),
+                       dim3(AUG_THREADS), 0, stream, img, labels, idx, aug,
+                       mix, lam, lut, static_cast<T*>(out), labels_a_out,
+                       labels_b_out, lam_out, N, M, H, W, pad,
+                       (int)channels_last);
+  }
+}
+
 }  // namespace
 
-std::tuple<at::Tensor, at::Tensor> batch_augment(
-    at::Tensor images_u8, at::Tensor labels_i64, at::Tensor idx_i32,
-    c10::optional<at::Tensor> aug_i32, at::Tensor lut_f32, long pad,
-    bool channels_last, at::ScalarType out_dtype) {
+// Argument checks shared by the two entry points; returns the aug table's
+// pointer, or nullptr for evaluation.
+static const int* check_batch_args(const at::Tensor& images_u8,
+                                   const at::Tensor& labels_i64,
+                                   const at::Tensor& idx_i32,
+                                   const c10::optional<at::Tensor>& aug_i32,
+                                   const at::Tensor& lut_f32, long pad,
+                                   at::ScalarType out_dtype) {
   TORCH_CHECK(images_u8.is_cuda(), "images_u8 must be a HIP tensor");
   TORCH_CHECK(images_u8.scalar_type() == at::kByte, "images_u8 must be uint8");
   TORCH_CHECK(images_u8.dim() == 4 && images_u8.size(3) == 3,
@@ -272,6 +490,18 @@ std::tuple<at::Tensor, at::Tensor> batch_augment(
   TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16 ||
               out_dtype == at::kHalf,
               "out_dtype must be float32, bfloat16 or float16");
+  return aug;
+}
+
+std::tuple<at::Tensor, at::Tensor> batch_augment(
+    at::Tensor images_u8, at::Tensor labels_i64, at::Tensor idx_i32,
+    c10::optional<at::Tensor> aug_i32, at::Tensor lut_f32, long pad,
+    bool channels_last, at::ScalarType out_dtype) {
+  const int* aug = check_batch_args(images_u8, labels_i64, idx_i32, aug_i32,
+                                    lut_f32, pad, out_dtype);
+  const long M = images_u8.size(0), H = images_u8.size(1),
+             W = images_u8.size(2);
+  const auto dev = images_u8.device();
 
   const long N = idx_i32.size(0);
   TORCH_CHECK(N < (1L << 31), "batch too large");
@@ -300,4 +530,56 @@ std::tuple<at::Tensor, at::Tensor> batch_augment(
         labels.data_ptr<long>(), (int)N, (int)M, (int)H, (int)W, (int)pad,
         channels_last, stream);
   return {images, labels};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> batch_augment_cutmix(
+    at::Tensor images_u8, at::Tensor labels_i64, at::Tensor idx_i32,
+    c10::optional<at::Tensor> aug_i32, at::Tensor mix_i32, at::Tensor lam_f32,
+    at::Tensor lut_f32, long pad, bool channels_last,
+    at::ScalarType out_dtype) {
+  const int* aug = check_batch_args(images_u8, labels_i64, idx_i32, aug_i32,
+                                    lut_f32, pad, out_dtype);
+  const long M = images_u8.size(0), H = images_u8.size(1),
+             W = images_u8.size(2);
+  const auto dev = images_u8.device();
+  TORCH_CHECK(H < (1L << 16) && W < (1L << 16),
+              "image sides must fit the box's 16-bit fields");
+  TORCH_CHECK(mix_i32.scalar_type() == at::kInt, "mix_i32 must be int32");
+  TORCH_CHECK(mix_i32.device() == dev && mix_i32.dim() == 2
+              && mix_i32.size(0) == M && mix_i32.size(1) == 3
+              && mix_i32.is_contiguous(),
+              "mix_i32 must be a contiguous [M, 3] tensor on the images' "
+              "device");
+  TORCH_CHECK(lam_f32.scalar_type() == at::kFloat, "lam_f32 must be float32");
+  TORCH_CHECK(lam_f32.device() == dev && lam_f32.dim() == 1
+              && lam_f32.size(0) == M && lam_f32.is_contiguous(),
+              "lam_f32 must be a contiguous [M] tensor on the images' device");
+
+  const long N = idx_i32.size(0);
+  TORCH_CHECK(N < (1L << 31), "batch too large");
+  at::DeviceGuard guard(dev);
+  auto images = at::empty(
+      {N, 3, H, W}, images_u8.options().dtype(out_dtype),
+      channels_last ? at::MemoryFormat::ChannelsLast
+                    : at::MemoryFormat::Contiguous);
+  auto labels_a = at::empty({N}, labels_i64.options());
+  auto labels_b = at::empty({N}, labels_i64.options());
+  auto lam = at::empty({N}, lam_f32.options());
+  if (N == 0) return {images, labels_a, labels_b, lam};
+
+  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  auto launch = [&](auto tag) {
+    using T = decltype(tag);
+    launch_batch_augment_cutmix<T>(
+        images_u8.data_ptr<unsigned char>(), labels_i64.data_ptr<long>(),
+        idx_i32.data_ptr<int>(), aug, mix_i32.data_ptr<int>(),
+        lam_f32.data_ptr<float>(), lut_f32.data_ptr<float>(),
+        images.data_ptr(), labels_a.data_ptr<long>(),
+        labels_b.data_ptr<long>(), lam.data_ptr<float>(), (int)N, (int)M,
+        (int)H, (int)W, (int)pad, channels_last, stream);
+  };
+  if (out_dtype == at::kFloat) launch(float{});
+  else if (out_dtype == at::kBFloat16) launch((unsigned short)0);
+  else launch(HalfBits{});
+  return {images, labels_a, labels_b, lam};
 }

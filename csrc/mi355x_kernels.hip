@@ -762,6 +762,94 @@ __global__ void xent_bwd_kernel(const scalar_t* __restrict__ logits,
 }
 
 // ---------------------------------------------------------------------------
+// Two-label smoothed cross entropy (CutMix targets + label smoothing):
+//   q_r  = (1-eps) * (l*x[r,a] + (1-l)*x[r,b]) + (eps/C) * sum_j x[r,j]
+//   loss = mean_r (lse_r - q_r)
+// i.e. l*CE(x,a) + (1-l)*CE(x,b) with torch's label_smoothing=eps. The max /
+// sum(exp) / lse part is xent_fwd_kernel's, statement for statement; the row
+// sum of x is a third block reduction in the same pass. Keep q in the form
+// above: with l = 1 and eps = 0 it is 1*xa + 0*xb + 0*sum == xa exactly, so
+// the kernel then gives xent_fwd_kernel's bits for any finite logits and any b.
+// A class outside [0, C) reads nothing and counts as a zero logit.
+// ---------------------------------------------------------------------------
+template <typename scalar_t>
+__global__ void xent_mix_fwd_kernel(const scalar_t* __restrict__ logits,
+                                    const long* __restrict__ target_a,
+                                    const long* __restrict__ target_b,
+                                    const float* __restrict__ lam,
+                                    float* __restrict__ lse_out,
+                                    float* __restrict__ row_loss,
+                                    float eps, int N, int C) {
+  __shared__ float lds[32];
+  const int row = blockIdx.x;
+  const scalar_t* xr = logits + (long)row * C;
+  float m = -INFINITY;
+  for (int j = threadIdx.x; j < C; j += blockDim.x)
+    m = fmaxf(m, (float)xr[j]);
+  {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wid = threadIdx.x / WAVE;
+    m = warp_reduce_max(m);
+    if (lane == 0) lds[wid] = m;
+    __syncthreads();
+    const int nw = (blockDim.x + WAVE - 1) / WAVE;
+    float v = (threadIdx.x < nw) ? lds[threadIdx.x] : -INFINITY;
+    if (wid == 0) v = warp_reduce_max(v);
+    if (threadIdx.x == 0) lds[31] = v;
+    __syncthreads();
+    m = lds[31];
+  }
+  __syncthreads();
+  float s = 0.f, sx = 0.f;
+  for (int j = threadIdx.x; j < C; j += blockDim.x) {
+    const float x = (float)xr[j];
+    s += __expf(x - m);
+    sx += x;
+  }
+  s = block_reduce_sum(s, lds);
+  __syncthreads();  // lds is reused by the next reduction
+  sx = block_reduce_sum(sx, lds);
+  if (threadIdx.x == 0) {
+    const float lse = m + __logf(s);
+    lse_out[row] = lse;
+    const long a = target_a[row], b = target_b[row];
+    const float xa = (unsigned long)a < (unsigned long)C ? (float)xr[a] : 0.f;
+    const float xb = (unsigned long)b < (unsigned long)C ? (float)xr[b] : 0.f;
+    const float l = lam[row];
+    const float q = (1.f - eps) * (l * xa + (1.f - l) * xb) + (eps / C) * sx;
+    row_loss[row] = (lse - q) / N;
+  }
+}
+
+// dx = (softmax(x) - (1-eps)*(l*[j==a] + (1-l)*[j==b]) - eps/C) * dloss / N;
+// a == b adds both one-hots. With l = 1, eps = 0 the subtracted terms are
+// exactly 1 or 0 and 0, which is xent_bwd_kernel's arithmetic.
+template <typename scalar_t>
+__global__ void xent_mix_bwd_kernel(const scalar_t* __restrict__ logits,
+                                    const long* __restrict__ target_a,
+                                    const long* __restrict__ target_b,
+                                    const float* __restrict__ lam,
+                                    const float* __restrict__ lse,
+                                    const float* __restrict__ dloss,
+                                    scalar_t* __restrict__ dx,
+                                    float eps, long total, int C) {
+  const float scale = dloss[0];
+  const float eps_c = eps / C;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long)gridDim.x * blockDim.x) {
+    const long row = i / C;
+    const int col = (int)(i % C);
+    float p = __expf((float)logits[i] - lse[row]);
+    const float l = lam[row];
+    const float ia = col == (int)target_a[row] ? 1.f : 0.f;
+    const float ib = col == (int)target_b[row] ? 1.f : 0.f;
+    const float t = (1.f - eps) * (l * ia + (1.f - l) * ib);
+    p = p - t - eps_c;
+    dx[i] = (scalar_t)(p * scale / (total / C));
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Multi-tensor SGD with momentum + weight decay (exact torch.optim.SGD math):
 //   m <- mu*m + g + wd*p ; p <- p - lr*m
 // Tensor pointers travel in kernel-arg space (no host->device table copies);
@@ -1813,6 +1901,73 @@ at::Tensor xent_bwd(at::Tensor logits, at::Tensor target, at::Tensor lse,
   return dx;
 }
 
+static void check_mix_targets(const at::Tensor& logits, const at::Tensor& ta,
+                              const at::Tensor& tb, const at::Tensor& lam,
+                              double eps) {
+  CHECK_CUDA(logits); CHECK_CONTIG(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1,
+              "logits must be a non-empty [N, C] tensor");
+  const long N = logits.size(0);
+  const auto dev = logits.device();
+  TORCH_CHECK(ta.scalar_type() == at::kLong && tb.scalar_type() == at::kLong,
+              "target_a and target_b must be int64");
+  TORCH_CHECK(lam.scalar_type() == at::kFloat, "lam must be float32");
+  TORCH_CHECK(ta.device() == dev && tb.device() == dev && lam.device() == dev,
+              "target_a, target_b and lam must be on the logits' device");
+  TORCH_CHECK(ta.dim() == 1 && ta.size(0) == N && ta.is_contiguous() &&
+              tb.dim() == 1 && tb.size(0) == N && tb.is_contiguous() &&
+              lam.dim() == 1 && lam.size(0) == N && lam.is_contiguous(),
+              "target_a, target_b and lam must be contiguous [N] tensors");
+  TORCH_CHECK(eps >= 0.0 && eps < 1.0, "label smoothing must be in [0, 1)");
+}
+
+std::vector<at::Tensor> xent_mix_fwd(at::Tensor logits, at::Tensor target_a,
+                                     at::Tensor target_b, at::Tensor lam,
+                                     double eps) {
+  check_mix_targets(logits, target_a, target_b, lam, eps);
+  const int N = logits.size(0), C = logits.size(1);
+  auto lse = at::empty({N}, logits.options().dtype(at::kFloat));
+  auto row_loss = at::empty({N}, logits.options().dtype(at::kFloat));
+  auto loss = at::empty({}, logits.options().dtype(at::kFloat));
+  const int threads = C <= 128 ? 64 : 256;
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::Half, at::ScalarType::BFloat16,
+      logits.scalar_type(), "xent_mix_fwd", [&] {
+    hipLaunchKernelGGL(xent_mix_fwd_kernel<scalar_t>, dim3(N), dim3(threads),
+                       0, cur_stream(),
+                       logits.data_ptr<scalar_t>(), target_a.data_ptr<long>(),
+                       target_b.data_ptr<long>(), lam.data_ptr<float>(),
+                       lse.data_ptr<float>(), row_loss.data_ptr<float>(),
+                       (float)eps, N, C);
+  });
+  hipLaunchKernelGGL(xent_mean_kernel, dim3(1), dim3(256), 0, cur_stream(),
+                     row_loss.data_ptr<float>(), loss.data_ptr<float>(), N);
+  return {loss, lse};
+}
+
+at::Tensor xent_mix_bwd(at::Tensor logits, at::Tensor target_a,
+                        at::Tensor target_b, at::Tensor lam, at::Tensor lse,
+                        at::Tensor dloss, double eps) {
+  check_mix_targets(logits, target_a, target_b, lam, eps);
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+              lse.numel() == logits.size(0) && lse.device() == logits.device(),
+              "lse must be the contiguous float32 [N] tensor of xent_mix_fwd");
+  const int C = logits.size(1);
+  const long total = logits.numel();
+  auto dx = at::empty_like(logits);
+  auto dloss_f = dloss.to(at::kFloat).contiguous();
+  const int blocks = (int)std::min((total + 255) / 256, (long)4096);
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::Half, at::ScalarType::BFloat16,
+      logits.scalar_type(), "xent_mix_bwd", [&] {
+    hipLaunchKernelGGL(xent_mix_bwd_kernel<scalar_t>, dim3(blocks), dim3(256),
+                       0, cur_stream(),
+                       logits.data_ptr<scalar_t>(), target_a.data_ptr<long>(),
+                       target_b.data_ptr<long>(), lam.data_ptr<float>(),
+                       lse.data_ptr<float>(), dloss_f.data_ptr<float>(),
+                       dx.data_ptr<scalar_t>(), (float)eps, total, C);
+  });
+  return dx;
+}
+
 void multi_tensor_sgd(std::vector<at::Tensor> params,
                       std::vector<at::Tensor> grads,
                       std::vector<at::Tensor> bufs,
@@ -2055,6 +2210,11 @@ std::tuple<at::Tensor, at::Tensor> batch_augment(
     at::Tensor images_u8, at::Tensor labels_i64, at::Tensor idx_i32,
     c10::optional<at::Tensor> aug_i32, at::Tensor lut_f32, long pad,
     bool channels_last, at::ScalarType out_dtype);
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> batch_augment_cutmix(
+    at::Tensor images_u8, at::Tensor labels_i64, at::Tensor idx_i32,
+    c10::optional<at::Tensor> aug_i32, at::Tensor mix_i32, at::Tensor lam_f32,
+    at::Tensor lut_f32, long pad, bool channels_last,
+    at::ScalarType out_dtype);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_build_wT", &conv_build_wT,
@@ -2109,6 +2269,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "BN backward apply from bn_bwd_tail's coeffs");
   m.def("xent_fwd", &xent_fwd, "fused softmax cross-entropy forward");
   m.def("xent_bwd", &xent_bwd, "fused softmax cross-entropy backward");
+  m.def("xent_mix_fwd", &xent_mix_fwd,
+        "two-label smoothed cross-entropy forward: lam*CE(a) + (1-lam)*CE(b) "
+        "with label smoothing eps -> (loss, lse)",
+        py::arg("logits"), py::arg("target_a"), py::arg("target_b"),
+        py::arg("lam"), py::arg("eps"));
+  m.def("xent_mix_bwd", &xent_mix_bwd,
+        "two-label smoothed cross-entropy backward",
+        py::arg("logits"), py::arg("target_a"), py::arg("target_b"),
+        py::arg("lam"), py::arg("lse"), py::arg("dloss"), py::arg("eps"));
   m.def("multi_tensor_sgd", &multi_tensor_sgd,
         "fused multi-tensor SGD step; w16s: per-param bf16|fp16 shadow (or "
         "None) "
@@ -2132,4 +2301,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("images_u8"), py::arg("labels_i64"), py::arg("idx_i32"),
         py::arg("aug_i32"), py::arg("lut_f32"), py::arg("pad"),
         py::arg("channels_last"), py::arg("out_dtype"));
+  m.def("batch_augment_cutmix", &batch_augment_cutmix,
+        "batch_augment with a CutMix box per sample: mix[i] = (partner dataset "
+        "index or -1, y0|y1<<16, x0|x1<<16), lam[i] -> (images, labels_a, "
+        "labels_b, lam)",
+        py::arg("images_u8"), py::arg("labels_i64"), py::arg("idx_i32"),
+        py::arg("aug_i32"), py::arg("mix_i32"), py::arg("lam_f32"),
+        py::arg("lut_f32"), py::arg("pad"), py::arg("channels_last"),
+        py::arg("out_dtype"));
 }

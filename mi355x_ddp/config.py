@@ -71,6 +71,13 @@ class TrainConfig:
     # random horizontal flip and exists on that path only
     device_data: bool = False
     hflip: bool = False
+    # regularisers beyond the reference's recipe. label_smoothing is the
+    # criterion's (applies whenever it is called, validation included, like
+    # nn.CrossEntropyLoss); CutMix lives in the device_data input kernel:
+    # alpha > 0 turns it on, each sample is mixed with probability prob
+    label_smoothing: float = 0.0
+    cutmix_alpha: float = 0.0
+    cutmix_prob: float = 0.5
 
     # native kernels
     native_ops: bool = True           # HIP kernels when extension present; fail loudly on GPU if absent
@@ -93,6 +100,18 @@ class TrainConfig:
         if self.hflip and not self.device_data:
             raise ValueError("hflip needs device_data: the DataLoader path "
                              "has no flip and would ignore it silently")
+        if self.cutmix_alpha < 0:
+            raise ValueError("cutmix_alpha must be >= 0 (0 turns CutMix "
+                             f"off), got {self.cutmix_alpha}")
+        if self.cutmix_alpha > 0 and not self.device_data:
+            raise ValueError("cutmix_alpha needs device_data: the DataLoader "
+                             "path has no CutMix and would ignore it silently")
+        if not 0.0 <= self.cutmix_prob <= 1.0:
+            raise ValueError("cutmix_prob must be in [0, 1], got "
+                             f"{self.cutmix_prob}")
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError("label_smoothing must be in [0, 1), got "
+                             f"{self.label_smoothing}")
 
     def per_rank_batch(self, world_size: int) -> int:
         return max(1, self.batch_size // max(1, world_size))
@@ -153,6 +172,14 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                         "crop/normalize kernel launch per batch")
     p.add_argument("--hflip", action="store_true",
                    help="random horizontal flip (needs --device_data)")
+    p.add_argument("--label_smoothing", default=None, type=float,
+                   help="label smoothing of the loss, in [0, 1); applies to "
+                        "the validation loss too")
+    p.add_argument("--cutmix_alpha", default=None, type=float,
+                   help="CutMix with boxes from Beta(alpha, alpha); 0 = off "
+                        "(needs --device_data)")
+    p.add_argument("--cutmix_prob", default=None, type=float,
+                   help="probability that a sample is mixed (default 0.5)")
     return p
 
 
@@ -194,5 +221,8 @@ def config_from_args(args: argparse.Namespace, **overrides) -> TrainConfig:
         kw["device_data"] = True
     if getattr(args, "hflip", False):
         kw["hflip"] = True
+    for name in ("label_smoothing", "cutmix_alpha", "cutmix_prob"):
+        if getattr(args, name, None) is not None:
+            kw[name] = getattr(args, name)
     kw.update(overrides)
     return TrainConfig(**kw)

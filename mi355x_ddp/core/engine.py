@@ -38,6 +38,20 @@ def _zero_grads(model, optimizer):
         optimizer.zero_grad(set_to_none=False)
 
 
+def _target_to(target, device):
+    """A target is a label tensor or a CutMix (labels_a, labels_b, lam)
+    tuple; both move and slice elementwise."""
+    if isinstance(target, (tuple, list)):
+        return tuple(t.to(device, non_blocking=True) for t in target)
+    return target.to(device, non_blocking=True)
+
+
+def _target_slice(target, sl):
+    if isinstance(target, tuple):
+        return tuple(t[sl] for t in target)
+    return target[sl]
+
+
 def train_one_epoch(model, loader, criterion, optimizer, epoch: int,
                     cfg: TrainConfig, device, scaler: Optional[DynamicLossScaler] = None,
                     sink: Optional[JsonlSink] = None, max_steps: Optional[int] = None) -> float:
@@ -60,7 +74,7 @@ def train_one_epoch(model, loader, criterion, optimizer, epoch: int,
             break
         watchdog.arm()
         images = images.to(device, non_blocking=True)
-        labels = labels.to(device, non_blocking=True)
+        labels = _target_to(labels, device)
         if cfg.channels_last:
             images = images.to(memory_format=torch.channels_last)
         _zero_grads(model, optimizer)
@@ -78,7 +92,8 @@ def train_one_epoch(model, loader, criterion, optimizer, epoch: int,
             log_loss = torch.zeros((), device=device)
             for a in range(accu):
                 sub_images = images[a * sub:(a + 1) * sub]
-                sub_labels = labels[a * sub:(a + 1) * sub]
+                sub_labels = _target_slice(labels,
+                                           slice(a * sub, (a + 1) * sub))
                 if sub_images.numel() == 0:
                     continue
                 is_last = a == accu - 1

@@ -80,7 +80,7 @@ def build_training(cfg: TrainConfig, device: torch.device, world_size: int,
         model = wrap_torch_ddp(model,
                                device.index if device.type == "cuda" else None,
                                bucket_cap_mb=cfg.bucket_cap_mb)
-    criterion = SoftmaxCrossEntropy().to(device)
+    criterion = SoftmaxCrossEntropy(cfg.label_smoothing).to(device)
     optimizer = FusedSGD(model.parameters(), lr=cfg.lr, momentum=cfg.momentum,
                          weight_decay=cfg.weight_decay)
     scheduler = build_scheduler(optimizer, cfg)

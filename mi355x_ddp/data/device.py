@@ -6,7 +6,10 @@ launch: no per-sample Python, no worker processes, no per-step host-to-device
 copy, no layout-conversion or autocast-cast kernel. Per EPOCH the host uploads
 two small int32 tensors: this rank's index list (torch's own
 DistributedSampler, so sharding is identical to the DataLoader path) and the
-augmentation table (``ops.draw_aug_params``).
+augmentation table (``ops.draw_aug_params``). With CutMix
+(``cutmix_alpha > 0``) two more small tables go up per epoch
+(``ops.draw_cutmix_params``) and the batches come from
+``ops.batch_augment_cutmix``, whose target is ``(labels_a, labels_b, lam)``.
 
 Unlike the DataLoader path (``cifar.py``), whose crop is seeded per index and
 therefore the same in every epoch, the augmentation here is redrawn each epoch
@@ -22,7 +25,9 @@ import torch
 from torch.utils.data.distributed import DistributedSampler
 
 from ..config import TrainConfig
-from ..ops.augment import batch_augment, build_norm_lut, draw_aug_params
+from ..ops.augment import (batch_augment, batch_augment_cutmix,
+                           build_norm_lut, draw_aug_params,
+                           draw_cutmix_params)
 from .cifar import _real_cifar_available
 
 # synthetic split sizes (CIFAR-100's)
@@ -94,16 +99,27 @@ class DeviceLoader:
     is not used) and, with ``augment``, draws that epoch's augmentation table.
     Both are uploaded once per epoch. ``drop_last`` applies to the sampler
     (trim rather than pad to a multiple of the world size) and to the last
-    short batch, as the train DataLoader it replaces does."""
+    short batch, as the train DataLoader it replaces does.
+
+    ``cutmix_alpha > 0`` turns CutMix on: each sample is mixed with
+    probability ``cutmix_prob`` with a partner drawn over the whole DATASET
+    (not the batch), so a sample's image is the same at every world size,
+    rank and batch size. Iterating then yields ``(images, (labels_a,
+    labels_b, lam))`` from one ``batch_augment_cutmix`` launch per batch."""
 
     def __init__(self, dataset: DeviceCIFAR, batch_size: int,
                  world_size: int = 1, rank: int = 0, shuffle: bool = False,
                  drop_last: bool = False, seed: int = 0, augment: bool = False,
                  pad: int = 4, hflip: bool = False,
                  channels_last: bool = False,
-                 out_dtype: torch.dtype = torch.float32):
+                 out_dtype: torch.dtype = torch.float32,
+                 cutmix_alpha: float = 0.0, cutmix_prob: float = 0.5):
         if batch_size < 1:
             raise ValueError("batch_size must be >= 1")
+        if cutmix_alpha < 0:
+            raise ValueError("cutmix_alpha must be >= 0")
+        if not 0.0 <= cutmix_prob <= 1.0:
+            raise ValueError("cutmix_prob must be in [0, 1]")
         self.dataset = dataset
         self.batch_size = batch_size
         self.drop_last = drop_last
@@ -113,6 +129,8 @@ class DeviceLoader:
         self.hflip = hflip
         self.channels_last = channels_last
         self.out_dtype = out_dtype
+        self.cutmix_alpha = cutmix_alpha
+        self.cutmix_prob = cutmix_prob
         self.sampler = DistributedSampler(
             range(len(dataset)), num_replicas=world_size, rank=rank,
             shuffle=shuffle, seed=seed, drop_last=drop_last)
@@ -120,6 +138,8 @@ class DeviceLoader:
         self.epoch: Optional[int] = None
         self.indices: Optional[torch.Tensor] = None   # int32 [len(sampler)]
         self.aug: Optional[torch.Tensor] = None       # int32 [M] or None
+        self.mix: Optional[torch.Tensor] = None       # int32 [M, 3] or None
+        self.lam: Optional[torch.Tensor] = None       # float32 [M] or None
 
     def set_epoch(self, epoch: int) -> None:
         self.sampler.set_epoch(epoch)
@@ -129,6 +149,12 @@ class DeviceLoader:
         self.aug = draw_aug_params(len(self.dataset), self.pad, self.hflip,
                                    self.seed, epoch).to(dev) \
             if self.augment else None
+        if self.cutmix_alpha > 0:
+            _, H, W, _ = self.dataset.images_u8.shape
+            mix, lam = draw_cutmix_params(len(self.dataset), H, W,
+                                          self.cutmix_alpha, self.cutmix_prob,
+                                          self.seed, epoch)
+            self.mix, self.lam = mix.to(dev), lam.to(dev)
         self.epoch = epoch
 
     def __len__(self) -> int:
@@ -142,6 +168,15 @@ class DeviceLoader:
             self.set_epoch(0)
         indices, aug, ds, bs = self.indices, self.aug, self.dataset, \
             self.batch_size
+        if self.cutmix_alpha > 0:
+            mix, lam = self.mix, self.lam
+            for b in range(len(self)):
+                images, labels_a, labels_b, lam_b = batch_augment_cutmix(
+                    ds.images_u8, ds.labels, indices[b * bs:(b + 1) * bs],
+                    aug, mix, lam, self.lut, self.pad, self.channels_last,
+                    self.out_dtype)
+                yield images, (labels_a, labels_b, lam_b)
+            return
         for b in range(len(self)):
             yield batch_augment(ds.images_u8, ds.labels,
                                 indices[b * bs:(b + 1) * bs], aug, self.lut,
@@ -184,7 +219,9 @@ def build_device_loaders(cfg: TrainConfig, world_size: int, rank: int,
                   out_dtype=amp_input_dtype(cfg.amp))
     train_loader = DeviceLoader(train_ds, per_rank, shuffle=True,
                                 drop_last=True, augment=True,
-                                hflip=cfg.hflip, **common)
+                                hflip=cfg.hflip,
+                                cutmix_alpha=cfg.cutmix_alpha,
+                                cutmix_prob=cfg.cutmix_prob, **common)
     test_loader = DeviceLoader(test_ds, per_rank, shuffle=False,
                                drop_last=False, augment=False, **common)
     return train_loader, test_loader, train_loader

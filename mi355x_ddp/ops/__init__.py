@@ -6,3 +6,4 @@ from .sgd import FusedSGD  # noqa: F401
 from .conv import MI355Conv2d, conv2d  # noqa: F401
 from .pool import GlobalAvgPool2d  # noqa: F401
 from .augment import batch_augment, build_norm_lut, draw_aug_params  # noqa: F401
+from .augment import batch_augment_cutmix, draw_cutmix_params  # noqa: F401

@@ -10,12 +10,17 @@ at batch 256 (the flagship configuration):
                        plus the host-to-device copy and the channels_last
                        conversion the engine does per step
                device: DeviceLoader, whole epochs including set_epoch
+               device+cutmix: the same with CutMix (--cutmix_alpha,
+                       --cutmix_prob; by default every sample is mixed, the
+                       most the kernel can be asked to read)
   train_epoch  steps/s of engine.train_one_epoch, the first --discard steps
                left out, fed by
                static: eight pinned prefabricated batches (what bench.py
                        times, run through the same engine loop)
                loader: the DataLoader path
                device: the --device_data path
+               device+cutmix: the --device_data path with CutMix, the loss
+                       taking (labels_a, labels_b, lam)
 
 Every measurement is repeated --repeats times, the variants alternating, and
 printed as one JSON line each so the spread is visible. Windows end in a
@@ -56,6 +61,10 @@ def parse_args():
     p.add_argument("--device_epochs", type=int, default=3,
                    help="whole epochs per input_only measurement of the "
                         "device path")
+    p.add_argument("--cutmix_alpha", type=float, default=1.0,
+                   help="Beta parameter of the device+cutmix variant")
+    p.add_argument("--cutmix_prob", type=float, default=1.0,
+                   help="share of samples the device+cutmix variant mixes")
     p.add_argument("--no-channels-last", dest="channels_last",
                    action="store_false", default=True)
     p.add_argument("--rehearse", action="store_true",
@@ -147,6 +156,8 @@ def main():
                       # one loss materialisation per window, at step 0
                       log_interval=1 << 30)
     cfg_dev = cfg.replace(device_data=True)
+    cfg_mix = cfg_dev.replace(cutmix_alpha=args.cutmix_alpha,
+                              cutmix_prob=args.cutmix_prob)
     base = {"arch": cfg.arch, "amp": cfg.amp, "batch": cfg.batch_size,
             "channels_last": cfg.channels_last,
             "num_workers": cfg.num_workers, "device": device.type}
@@ -158,6 +169,8 @@ def main():
 
     old_loader, _, _ = build_loaders(cfg, 1, 0, distributed=False)
     new_loader, _, _ = build_loaders(cfg_dev, 1, 0, distributed=False,
+                                     device=device)
+    mix_loader, _, _ = build_loaders(cfg_mix, 1, 0, distributed=False,
                                      device=device)
 
     gen = torch.Generator().manual_seed(123)
@@ -182,12 +195,19 @@ def main():
                                    r * args.device_epochs)
         emit(row="input_only", path="device", repeat=r, batches=n,
              images_per_sec=round(ips, 1))
+        ips, n = input_only_device(mix_loader, cfg, device,
+                                   args.device_epochs,
+                                   r * args.device_epochs)
+        emit(row="input_only", path="device+cutmix", repeat=r, batches=n,
+             images_per_sec=round(ips, 1), cutmix_alpha=cfg_mix.cutmix_alpha,
+             cutmix_prob=cfg_mix.cutmix_prob)
 
-    # ---- the training loop fed three ways ---------------------------------
+    # ---- the training loop fed four ways ----------------------------------
     model, crit, opt, sched, scaler = build_training(
         cfg, device, 1, 0, distributed=True, wrap="flat")
     sources = (("static", static, cfg), ("loader", old_loader, cfg),
-               ("device", new_loader, cfg_dev))
+               ("device", new_loader, cfg_dev),
+               ("device+cutmix", mix_loader, cfg_mix))
     # every path once untimed: kernel selection, code objects, workers
     for name, source, run_cfg in sources:
         train_window(source, model, crit, opt, run_cfg, device,
