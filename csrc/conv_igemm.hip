@@ -135,12 +135,28 @@ __device__ __forceinline__ void decode_m2(int m, const ConvDims& d,
 // with it the per-pass re-reads of the gathered A operand — for the wide-N
 // high-C shapes (ResNet50's 1x1 expansions), where fwd/dgrad is A-traffic
 // bound.
+// SPLITK (FAST, MODE 0/1, 128x128 only): split-K for the small-M late stages,
+// where 128x128 tiles alone leave most CUs without a block. blockIdx.z is the
+// slice; slice z runs the pipelined K loop over its own contiguous range of
+// BK tiles (balanced: ranges differ by at most one tile; the host keeps
+// gridDim.z <= K / BK, so none is empty) and dumps its fp32 accumulators in
+// fragment order into a private slab, as the wgrad kernels do (see
+// store_frag_slab): `out` then points at the fp32 slabs, not at the 16-bit
+// output. No atomics, no zero-init; igemm_reduce_frag_kernel sums the slices
+// and rounds once.
+template <int NF>
+__device__ __forceinline__ void store_frag_slab(float* __restrict__ dwp,
+                                                const f32x4* acc, int tid);
+
 template <typename T, int MODE, bool FAST, int BMT = BM, bool PADC = false,
-          int BNT = BN>
+          int BNT = BN, bool SPLITK = false>
 __global__ __launch_bounds__(256)
 void conv_igemm_kernel(const T* __restrict__ Ag,
                        const T* __restrict__ Bg,
                        T* __restrict__ out, ConvDims d) {
+  static_assert(!SPLITK || (FAST && MODE != 2 && !PADC && BMT == 128 &&
+                            BNT == 128),
+                "split-K exists for the pipelined 128x128 tile only");
   typedef typename Elem16<T>::x8 x8;
   constexpr int MI = BMT / 32;
   constexpr int NI = BNT / 32;
@@ -285,16 +301,26 @@ void conv_igemm_kernel(const T* __restrict__ Ag,
     // Register-pipelined: tile k+1's global loads issue before tile k's
     // MFMAs, so HBM/L2 latency overlaps compute; the waits land at the LDS
     // write after the barrier (write-after-barrier form).
+    int kbeg = 0, kend = d.K;
+    if constexpr (SPLITK) {
+      // slice z of S takes tiles [z*q + min(z, r), +q + (z < r)), q = T / S,
+      // r = T % S: the first r slices are one tile longer
+      const int nkt = d.K / BK, S = (int)gridDim.z, z = (int)blockIdx.z;
+      const int q = nkt / S, r = nkt - q * S;
+      const int t0 = z * q + min(z, r);
+      kbeg = t0 * BK;
+      kend = (t0 + q + (z < r ? 1 : 0)) * BK;
+    }
     {
       float4 a0, a1, a2, a3, b0, b1, b2, b3;
-      issue_A(0, a0, a1, a2, a3);
-      issue_B(0, b0, b1, b2, b3);
+      issue_A(kbeg, a0, a1, a2, a3);
+      issue_B(kbeg, b0, b1, b2, b3);
       write_A(a0, a1, a2, a3);
       write_B(b0, b1, b2, b3);
     }
     __syncthreads();
-    for (int kk0 = 0; kk0 < d.K; kk0 += BK) {
-      const bool has_next = kk0 + BK < d.K;
+    for (int kk0 = kbeg; kk0 < kend; kk0 += BK) {
+      const bool has_next = kk0 + BK < kend;
       float4 a0 = {}, a1 = {}, a2 = {}, a3 = {};
       float4 b0 = {}, b1 = {}, b2 = {}, b3 = {};
       if (has_next) {
@@ -357,6 +383,13 @@ void conv_igemm_kernel(const T* __restrict__ Ag,
       mfma_tile();
       __syncthreads();
     }
+  }
+
+  if constexpr (SPLITK) {
+    // edge tiles included: rows / columns past M / N hold what the clamped
+    // loads accumulated and are dropped by the reduce
+    store_frag_slab<MI * NI>(reinterpret_cast<float*>(out), &acc[0][0], tid);
+    return;
   }
 
   // ---- epilogue: D row = (lane>>4)*4 + reg, col = lane&15 ----------------
@@ -1131,6 +1164,81 @@ void wgrad_reduce_frag_kernel(const float* __restrict__ part,
       store_dw<T>(dw, f32, (long)(m + r0 + r) * Nout + nout, s[r]);
 }
 
+// Reduce for the split-K fwd / dgrad slabs (conv_igemm_kernel<.., SPLITK>):
+// out[m][n] = round(sum over z = 0, 1, .., S-1 of slab z), fp32 adds in that
+// fixed order, one rounding to T, so a (shape, splits) pair always gives the
+// same bits. A sibling of wgrad_reduce_frag_kernel<T, 1, 4>, not a reuse: that
+// kernel gives a thread one slot (4 rows of ONE column), i.e. 2-byte stores
+// 32 bytes apart across a wave. The output here is the activation-sized
+// [M][N] tensor, so a thread takes the 8 consecutive slots of a lane octet
+// instead — 4 rows x 8 consecutive channels, 128 contiguous bytes per slice
+// to load and one 16-byte store per row — and threads are numbered so that 16
+// consecutive threads cover one 256-byte row segment of the 128x128 tile.
+// Thread q of a tile: column octet co = q & 15, row quad rq = q >> 4; the
+// slot follows from the accumulator map of the 128x128 tile (wave order
+// wm = (wave >> 1) * 64, wn = (wave & 1) * 64, f = mi * 4 + ni, row =
+// (lane >> 4) * 4 + reg, col = lane & 15). Rows / columns past M / N (edge
+// tiles) are dropped; N % 8 != 0 stores element by element.
+template <typename T>
+__global__ __launch_bounds__(256)
+void igemm_reduce_frag_kernel(const float* __restrict__ part,
+                              T* __restrict__ out, int M, int N, int tn,
+                              long nslots, int splits) {
+  typedef typename Elem16<T>::x8 x8;
+  const long u = (long)blockIdx.x * 256 + threadIdx.x;  // grid = 2 * ntiles
+  const int tile = (int)(u >> 9);
+  const int q = (int)(u & 511);
+  const int co = q & 15, rq = q >> 4;
+  const int wave = ((rq >> 4) << 1) | (co >> 3);
+  const int f = ((rq >> 2) & 3) * 4 + ((co >> 1) & 3);
+  const int lane0 = (rq & 3) * 16 + (co & 1) * 8;
+  const f32x4* p = (const f32x4*)part + (long)tile * 4096 + f * 256 +
+                   wave * 64 + lane0;
+  f32x4 s[8], cur[8], nxt[8];
+  #pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    s[j] = p[j];
+    cur[j] = nxt[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  if (splits > 1) {
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) cur[j] = p[nslots + j];
+  }
+  for (int z = 1; z < splits; ++z) {
+    const bool more = z + 1 < splits;
+    if (more) {   // slice z+1 in flight while slice z is added
+      #pragma unroll
+      for (int j = 0; j < 8; ++j) nxt[j] = p[(long)(z + 1) * nslots + j];
+    }
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) s[j] += cur[j];
+    if (more) {
+      #pragma unroll
+      for (int j = 0; j < 8; ++j) cur[j] = nxt[j];
+    }
+  }
+  const int by = tile / tn, bx = tile - by * tn;
+  const int m = by * 128 + rq * 4;
+  const int n = bx * 128 + co * 8;
+  if (n >= N) return;
+  const bool vec = (N & 7) == 0;   // then n + 8 <= N and rows are 16 B aligned
+  #pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    if (m + r >= M) continue;
+    T* dst = out + (long)(m + r) * N + n;
+    if (vec) {
+      x8 v;
+      #pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = Elem16<T>::from_float(s[j][r]);
+      *(x8*)dst = v;
+    } else {
+      #pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (n + j < N) dst[j] = Elem16<T>::from_float(s[j][r]);
+    }
+  }
+}
+
 // wT[c][i][j][k] = w[k][R-1-i][S-1-j][c] — the 180°-rotated transposed filter
 // the dgrad GEMM consumes, built in ONE kernel (the ATen flip+permute+copy
 // chain was 3 launches per conv backward). This kernel, the 16-bit source path
@@ -1445,11 +1553,42 @@ inline int pick_bmt(const ConvDims& d, long tile) {
   return tiles128 < 384 ? 64 : 128;  // small-M: halve tile, double blocks
 }
 
+// Split-K for the 128x128 fwd / dgrad tile (tile == 228 with splits > 1; the
+// caller has checked FAST and N >= 96). The request is clamped so that every
+// slice has at least one BK tile and the slabs stay under ~96 MB; 1 means
+// "launch the unsplit kernel".
+inline int igemm_splits(const ConvDims& d, long splits) {
+  const long tiles = (long)((d.M + 127) / 128) * ((d.N + 127) / 128);
+  const long max_ws = std::max(1L, 96L * 1024 * 1024 / (tiles * 128 * 128 * 4));
+  return (int)std::max(1L, std::min({splits, (long)(d.K / BK), max_ws}));
+}
+
+// One split-K launch + one reduce. The slabs are whole tiles in fragment
+// order (see store_frag_slab), allocated from the caching allocator on the
+// conv stream, so a hipGraph capture of the step still works.
+template <typename T, int MODE>
+void igemm_splitk_launch(const at::Tensor& a, const at::Tensor& b,
+                         at::Tensor& out, const ConvDims& d, int splits) {
+  auto stream = conv_stream();
+  const int tn = (d.N + 127) / 128, tm = (d.M + 127) / 128;
+  const long nslots = (long)tm * tn * 4096;   // f32x4 per slice
+  auto part = at::empty({(long)splits * nslots * 4},
+                        a.options().dtype(at::kFloat));
+  hipLaunchKernelGGL(
+      (conv_igemm_kernel<T, MODE, true, 128, false, 128, true>),
+      dim3(tn, tm, splits), dim3(256), 0, stream, ptr16<T>(a), ptr16<T>(b),
+      reinterpret_cast<T*>(part.data_ptr()), d);
+  hipLaunchKernelGGL(igemm_reduce_frag_kernel<T>, dim3(2 * tm * tn), dim3(256),
+                     0, stream, part.data_ptr<float>(),
+                     reinterpret_cast<T*>(out.data_ptr()), d.M, d.N, tn,
+                     nslots, splits);
+}
+
 // The three passes are written once over the element type T; the public
 // wrappers below check the operands and pick T from their (shared) dtype.
 template <typename T>
 at::Tensor conv_fwd_igemm_t(at::Tensor x, at::Tensor w, long stride, long pad,
-                            long tile) {
+                            long tile, long splits) {
   const int Nb = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int K = w.size(0), R = w.size(2), S = w.size(3);
   TORCH_CHECK(w.size(1) == C, "channel mismatch");
@@ -1494,6 +1633,11 @@ at::Tensor conv_fwd_igemm_t(at::Tensor x, at::Tensor w, long stride, long pad,
              Nb * P * Q, K, R * S * C};
   const bool fast = (C % BK == 0);
   if (tile == 228 && fast && d.N >= 96) {
+    const int nz = igemm_splits(d, splits);
+    if (nz > 1) {
+      igemm_splitk_launch<T, 0>(x, w, out, d, nz);
+      return out;
+    }
     // 128x128 tile: halves the N-tile count and with it the A re-reads
     const dim3 grid((d.N + 127) / 128, (d.M + 127) / 128);
     hipLaunchKernelGGL((conv_igemm_kernel<T, 0, true, 128, false, 128>), grid,
@@ -1516,19 +1660,22 @@ at::Tensor conv_fwd_igemm_t(at::Tensor x, at::Tensor w, long stride, long pad,
 
 // out (N,K,P,Q) channels_last <- x (N,C,H,W) channels_last, w (K,C,R,S)
 // channels_last (memory [K][R][S][C]); bf16 or fp16, out in the same dtype.
+// splits > 1 together with tile 228: split-K over that many slices (clamped,
+// see igemm_splits); every other tile, and a shape the 128x128 tile does not
+// take, ignores it.
 at::Tensor conv_fwd_igemm(at::Tensor x, at::Tensor w, long stride, long pad,
-                          long tile) {
+                          long tile, long splits) {
   check_nhwc_16(x, "x"); check_nhwc_16(w, "w");
   check_same_16(x, "x", w, "w");
   return x.scalar_type() == at::kHalf
-      ? conv_fwd_igemm_t<_Float16>(x, w, stride, pad, tile)
-      : conv_fwd_igemm_t<__bf16>(x, w, stride, pad, tile);
+      ? conv_fwd_igemm_t<_Float16>(x, w, stride, pad, tile, splits)
+      : conv_fwd_igemm_t<__bf16>(x, w, stride, pad, tile, splits);
 }
 
 namespace {
 template <typename T>
 at::Tensor conv_dgrad_igemm_t(at::Tensor dy, at::Tensor wT, long H, long W,
-                              long stride, long pad, long tile) {
+                              long stride, long pad, long tile, long splits) {
   const int Nb = dy.size(0), K = dy.size(1), P = dy.size(2), Q = dy.size(3);
   const int C = wT.size(0), R = wT.size(1), S = wT.size(2);
   TORCH_CHECK(wT.size(3) == K, "channel mismatch");
@@ -1564,6 +1711,11 @@ at::Tensor conv_dgrad_igemm_t(at::Tensor dy, at::Tensor wT, long H, long W,
     return dx;
   }
   if (tile == 228 && fast && d.N >= 96) {
+    const int nz = igemm_splits(d, splits);
+    if (nz > 1) {
+      igemm_splitk_launch<T, 1>(dy, wT, dx, d, nz);
+      return dx;
+    }
     const dim3 grid((d.N + 127) / 128, (d.M + 127) / 128);
     hipLaunchKernelGGL((conv_igemm_kernel<T, 1, true, 128, false, 128>), grid,
                        dim3(256), 0, conv_stream(), ptr16<T>(dy), ptr16<T>(wT),
@@ -1585,16 +1737,17 @@ at::Tensor conv_dgrad_igemm_t(at::Tensor dy, at::Tensor wT, long H, long W,
 
 // dx (N,C,H,W) channels_last <- dy (N,K,P,Q) channels_last,
 // wT (C,R,S,K) CONTIGUOUS with taps 180°-rotated (built by the Python side);
-// bf16 or fp16, dx in the same dtype.
+// bf16 or fp16, dx in the same dtype. splits: as for conv_fwd_igemm; the
+// stride-2 parity path ignores it.
 at::Tensor conv_dgrad_igemm(at::Tensor dy, at::Tensor wT, long H, long W,
-                            long stride, long pad, long tile) {
+                            long stride, long pad, long tile, long splits) {
   check_nhwc_16(dy, "dy");
   TORCH_CHECK(wT.is_cuda() && is_16bit(wT) && wT.is_contiguous(),
               "wT must be a contiguous bf16 or fp16 HIP tensor");
   check_same_16(dy, "dy", wT, "wT");
   return dy.scalar_type() == at::kHalf
-      ? conv_dgrad_igemm_t<_Float16>(dy, wT, H, W, stride, pad, tile)
-      : conv_dgrad_igemm_t<__bf16>(dy, wT, H, W, stride, pad, tile);
+      ? conv_dgrad_igemm_t<_Float16>(dy, wT, H, W, stride, pad, tile, splits)
+      : conv_dgrad_igemm_t<__bf16>(dy, wT, H, W, stride, pad, tile, splits);
 }
 
 // dw (K,C,R,S) channels_last <- dy, x; in their 16-bit dtype, or with out_fp32

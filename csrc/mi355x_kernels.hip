@@ -2195,9 +2195,9 @@ at::Tensor class_rank(at::Tensor logits, at::Tensor target) {
 // csrc/conv_igemm.hip — implicit-GEMM MFMA convolution (NHWC bf16 or fp16)
 at::Tensor conv_build_wT(at::Tensor w);
 at::Tensor conv_fwd_igemm(at::Tensor x, at::Tensor w, long stride, long pad,
-                          long tile);
+                          long tile, long splits);
 at::Tensor conv_dgrad_igemm(at::Tensor dy, at::Tensor wT, long H, long W,
-                            long stride, long pad, long tile);
+                            long stride, long pad, long tile, long splits);
 at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
                             long stride, long pad, long splits, long wtile,
                             bool out_fp32);
@@ -2220,14 +2220,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_build_wT", &conv_build_wT,
         "build rotated/transposed filter for dgrad (one launch)");
   m.def("conv_fwd_igemm", &conv_fwd_igemm,
-        "implicit-GEMM conv forward (NHWC bf16|fp16, MFMA); tile 0=auto|64|128",
+        "implicit-GEMM conv forward (NHWC bf16|fp16, MFMA); "
+        "tile 0=auto|64|128|228 (128x128); splits > 1 with tile 228: split-K "
+        "slices + one reduce",
         py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad"),
-        py::arg("tile") = 0);
+        py::arg("tile") = 0, py::arg("splits") = 1);
   m.def("conv_dgrad_igemm", &conv_dgrad_igemm,
         "implicit-GEMM conv input-grad (NHWC bf16|fp16, MFMA); "
-        "tile 0=auto|64|128",
+        "tile 0=auto|64|128|228 (128x128); splits > 1 with tile 228: split-K "
+        "slices + one reduce (not on the stride-2 parity path)",
         py::arg("dy"), py::arg("wT"), py::arg("H"), py::arg("W"),
-        py::arg("stride"), py::arg("pad"), py::arg("tile") = 0);
+        py::arg("stride"), py::arg("pad"), py::arg("tile") = 0,
+        py::arg("splits") = 1);
   m.def("conv_wgrad_igemm", &conv_wgrad_igemm,
         "implicit-GEMM conv weight-grad -> channels_last (K,C,R,S) in the "
         "input dtype; "

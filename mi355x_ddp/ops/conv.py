@@ -15,7 +15,11 @@ Autotune (the ``cudnn.benchmark=True`` equivalent the reference relies on,
 distributed.py:48): per conv shape, the GEMM-M tile (64 vs 128) for
 fwd/dgrad and the split-K factor for wgrad are measured once at first use
 with hip events and cached for the rest of the process. ``MI355X_AUTOTUNE=0``
-falls back to the static size heuristic inside the kernels.
+falls back to the static size heuristic inside the kernels. For the late
+small-M stages, where 128x128 tiles alone leave most CUs without a block, the
+fwd/dgrad candidates include that tile with the reduction split in 2 or 4
+slices (``splitk_candidates``); ``MI355X_CONV_SPLITK=0`` removes them (the
+A/B switch for the split-K kernels). The heuristic never picks a split.
 
 Weight shadows. Under 16-bit autocast an fp32 conv weight is needed in two
 other forms: its copy in the autocast dtype (forward, wgrad) and the
@@ -61,6 +65,10 @@ _NATIVE_DTYPES = (torch.bfloat16, torch.float16)
 
 def autotune_wanted() -> bool:
     return os.environ.get("MI355X_AUTOTUNE", "1") == "1"
+
+
+def conv_splitk_wanted() -> bool:
+    return os.environ.get("MI355X_CONV_SPLITK", "1") == "1"
 
 
 def weight_shadows_wanted() -> bool:
@@ -128,22 +136,29 @@ def _measure_ms(fn: Callable[[], None], iters: int = 4,
     return start.elapsed_time(stop) / iters
 
 
-def _tuned_choice(key: Tuple, candidates: Sequence,
+def _tuned_choice(key: Tuple,
+                  candidates: Union[Sequence, Callable[[], Sequence]],
                   run: Callable, default=None):
     """Cached fastest candidate for this shape key.
 
     `default` (first candidate unless given) is returned without measuring
     when autotune is off or a hipGraph capture is in flight — for the native
-    kernels that is the launch-config heuristic, never MIOpen.
+    kernels that is the launch-config heuristic, never MIOpen. `candidates`
+    may be a callable that returns them: it runs on a cache miss only.
     """
     if key in _TUNE_CACHE:
         return _TUNE_CACHE[key]
     # NB: is_current_stream_capturing() raises on CPU-only machines — check
     # the cheap conditions first (the tuner is only reached from GPU paths,
     # but keep it robust for direct callers/tests)
-    if (not autotune_wanted() or not torch.cuda.is_available() or
-            torch.cuda.is_current_stream_capturing()):
-        return candidates[0] if default is None else default
+    off = (not autotune_wanted() or not torch.cuda.is_available() or
+           torch.cuda.is_current_stream_capturing())
+    if off and default is not None:
+        return default
+    if callable(candidates):
+        candidates = candidates()
+    if off:
+        return candidates[0]
     best, best_ms = candidates[0], float("inf")
     for c in candidates:
         # a candidate already 2x slower than the best can't win — one
@@ -154,6 +169,60 @@ def _tuned_choice(key: Tuple, candidates: Sequence,
             best, best_ms = c, ms
     _TUNE_CACHE[key] = best
     return best
+
+
+TILE_128X128 = 228   # the kernels' name for the 128x128 fwd/dgrad tile
+_SPLITK_COUNTS = (2, 4)
+_SPLITK_MIN_KTILES = 4    # reduction tiles (of 64) a slice must keep
+
+
+def splitk_candidates(kind: str, x_shape, w_shape, stride: int, padding: int,
+                      cus: int) -> Tuple[Tuple[int, int], ...]:
+    """The (tile, splits) candidates the tuner adds for one fwd or dgrad pass:
+    a plain function of the shapes, so it can be tested without a GPU.
+
+    `x_shape` is the conv input (N, C, H, W) and `w_shape` the filter
+    (K, C, R, S), for both kinds. Split-K is offered only where it can pay:
+    - the pass takes the pipelined 128x128 kernel: gathered channels a
+      multiple of 64 and at least 96 GEMM columns; a stride-2 input-grad
+      with even H, W runs the parity kernels, which have no split form;
+    - the 128x128 tiles alone do not fill the chip: their count is at most
+      `cus`, the device's CU count;
+    - every slice keeps at least 4 reduction tiles of 64.
+    """
+    if not conv_splitk_wanted() or kind not in ("fwd", "dgrad"):
+        return ()
+    n, c, h, w = (int(v) for v in x_shape)
+    k, r, s = int(w_shape[0]), int(w_shape[2]), int(w_shape[3])
+    if kind == "fwd":
+        p = (h + 2 * padding - r) // stride + 1
+        q = (w + 2 * padding - s) // stride + 1
+        gm, gn, gathered = n * p * q, k, c
+    else:
+        if stride == 2 and h % 2 == 0 and w % 2 == 0:
+            return ()
+        gm, gn, gathered = n * h * w, c, k
+    if gathered % 64 != 0 or gn < 96:
+        return ()
+    tiles = -(-gm // 128) * -(-gn // 128)
+    if tiles > cus:
+        return ()
+    ktiles = r * s * gathered // 64
+    return tuple((TILE_128X128, z) for z in _SPLITK_COUNTS
+                 if ktiles // z >= _SPLITK_MIN_KTILES)
+
+
+def _cu_count(t: torch.Tensor) -> int:
+    return torch.cuda.get_device_properties(t.device).multi_processor_count
+
+
+def _choice_label(choice) -> str:
+    if choice == MIOPEN:
+        return "MIOpen"
+    if isinstance(choice, tuple) and len(choice) == 2 and \
+            choice[0] == TILE_128X128:
+        return f"128x128 tile, split-K x{choice[1]}"
+    return str(choice)
 
 
 def _tune_key(kind: str, dtype: torch.dtype, *shape) -> Tuple:
@@ -172,7 +241,9 @@ def tune_report() -> str:
     lines = []
     for key in sorted(_TUNE_CACHE, key=str):
         choice = _TUNE_CACHE[key]
-        label = "MIOpen" if choice == MIOPEN else str(choice)
+        # wgrad choices are (wtile, splits) pairs too, printed as they are
+        label = _choice_label(choice) if key[0] in ("fwd", "dgrad") \
+            else ("MIOpen" if choice == MIOPEN else str(choice))
         # _ConvIGEMM's keys carry the dtype of the pass's operands at [1]
         if len(key) > 1 and isinstance(key[1], torch.dtype):
             dt, rest = str(key[1]).replace("torch.", ""), key[2:]
@@ -328,13 +399,20 @@ class _ConvIGEMM(torch.autograd.Function):
         def run(t):
             if t == MIOPEN:
                 return F.conv2d(x, weight, None, stride, padding)
+            if isinstance(t, tuple):     # (tile, split-K slices)
+                return C.conv_fwd_igemm(x, weight, stride, padding, *t)
             return C.conv_fwd_igemm(x, weight, stride, padding, t)
 
         # the dtype is part of every key: a choice measured for bf16 is never
         # replayed for fp16 in the same process
         key = _tune_key("fwd", x.dtype, x.shape, weight.shape, stride,
                         padding)
-        return run(_tuned_choice(key, (64, 128, 228, MIOPEN), run, default=0))
+        def cands():
+            return (64, 128, TILE_128X128) + splitk_candidates(
+                "fwd", x.shape, weight.shape, stride, padding,
+                _cu_count(x)) + (MIOPEN,)
+
+        return run(_tuned_choice(key, cands, run, default=0))
 
     @staticmethod
     def backward(ctx, dy):
@@ -355,13 +433,18 @@ class _ConvIGEMM(torch.autograd.Function):
                         dy, x, weight, None,
                         [ctx.stride, ctx.stride], [ctx.padding, ctx.padding],
                         [1, 1], False, [0, 0], 1, [True, False, False])[0]
+                tile, nz = t if isinstance(t, tuple) else (t, 1)
                 return C.conv_dgrad_igemm(dy, wT, x.shape[2], x.shape[3],
-                                          ctx.stride, ctx.padding, t)
+                                          ctx.stride, ctx.padding, tile, nz)
 
             key = _tune_key("dgrad", x.dtype, dy.shape, wT.shape,
                             ctx.stride, ctx.padding)
-            dx = run_dx(_tuned_choice(key, (64, 128, 228, MIOPEN), run_dx,
-                                      default=0))
+            def cands_dx():
+                return (64, 128, TILE_128X128) + splitk_candidates(
+                    "dgrad", x.shape, weight.shape, ctx.stride, ctx.padding,
+                    _cu_count(x)) + (MIOPEN,)
+
+            dx = run_dx(_tuned_choice(key, cands_dx, run_dx, default=0))
         if ctx.needs_input_grad[1]:
             R = weight.shape[2]
 

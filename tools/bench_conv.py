@@ -9,6 +9,11 @@ MI355X box; output goes to stdout (redirect into gpurun_out/).
 Default: the ResNet18 CIFAR table (round-1 baseline format). --arch/--image-
 size collects the shape set from the actual model with forward hooks, e.g.
 `--arch resnet50 --image-size 224 --batch 64` for BASELINE config 5.
+
+The fwd / dgrad `best` column also sweeps the split-K candidates of the
+128x128 tile that the tuner would offer for the shape (cfg `(228, s)`); for
+each one it runs, a `# splitk` line gives its time and its relative error
+norm(a-b)/norm(b) against the unsplit tile=228 output of the same operands.
 """
 import argparse
 import os
@@ -87,6 +92,8 @@ def main():
                         "kernels and the MIOpen column alike")
     args = p.parse_args()
     from mi355x_ddp import _C
+    from mi355x_ddp.ops.conv import splitk_candidates
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
 
     dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
     print(f"# dtype {args.dtype}, batch {args.batch}")
@@ -129,12 +136,31 @@ def main():
                     best, bcfg = t, cand
             return best, str(bcfg)
 
+        def split_sweep(pss, run):
+            """Time the shape's split-K candidates; report each one's error
+            against the unsplit 128x128 tile."""
+            best, bcfg = float("inf"), None
+            base = None
+            for cand in splitk_candidates(pss, x.shape, wt.shape, stride, pad,
+                                          cus):
+                if base is None:
+                    base = run(228, 1).float()
+                t = timeit(lambda: run(*cand), warmup=2, iters=args.iters)
+                err = ((run(*cand).float() - base).norm() / base.norm()).item()
+                print(f"# splitk {name:>10} {pss:>6} {str(cand):>9} "
+                      f"{t:9.1f} us  rel err vs 228: {err:.3e}", flush=True)
+                if t < best:
+                    best, bcfg = t, cand
+            return best, str(bcfg)
+
         kw = dict(warmup=args.warmup, iters=args.iters)
         # fwd
         tm = timeit(lambda: F.conv2d(x, wt, None, stride, pad), **kw)
         ti = timeit(lambda: _C.conv_fwd_igemm(x, wt, stride, pad), **kw)
         tb, cfg = sweep((64, 128, 228),
                         lambda t: _C.conv_fwd_igemm(x, wt, stride, pad, t))
+        tb, cfg = min((tb, cfg), split_sweep(
+            "fwd", lambda t, s: _C.conv_fwd_igemm(x, wt, stride, pad, t, s)))
         row("fwd", tm, ti, tb, cfg)
         # dgrad (skip stem: input grad never needed there)
         if c != 3:
@@ -146,6 +172,9 @@ def main():
                         **kw)
             tb, cfg = sweep((64, 128, 228), lambda t: _C.conv_dgrad_igemm(
                 dy, wT, h, w, stride, pad, t))
+            tb, cfg = min((tb, cfg), split_sweep(
+                "dgrad", lambda t, s: _C.conv_dgrad_igemm(
+                    dy, wT, h, w, stride, pad, t, s)))
             row("dgrad", tm, ti, tb, cfg)
         # wgrad: sweep tile variants x split factors
         tm = timeit(lambda: torch.ops.aten.convolution_backward(
