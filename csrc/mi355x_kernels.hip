@@ -998,6 +998,270 @@ __global__ void multi_tensor_sgd_o2_kernel(MTMixedList tl, float lr, float mu,
 }
 
 // ---------------------------------------------------------------------------
+// Per-tensor squared L2 norms of weights and gradients, for LARS and for
+// clipping by the global gradient norm. Same chunking as the SGD kernel: block
+// b reduces chunk b of its tensor and stores the two sums at its global chunk
+// index in `partials` ([2][total_chunks]: weights, then gradients); the fold
+// kernel, one block per tensor, sums a tensor's partials into sq ([2][n]).
+// No atomics: every sum has a fixed order, so two runs agree bit for bit.
+// w is fp32 (the parameter or the O2 master); g is fp32 or bf16.
+//
+// Additions on the longest path to one sq value: MT_CHUNK/256 = 32 in a
+// thread, 6 + 6 in block_reduce_sum, then ceil(nchunks/256) in a fold thread
+// and 6 + 6 again: 56 + ceil(nchunks/256).
+// ---------------------------------------------------------------------------
+struct MTNormList {
+  const float* w[MT_MAX_TENSORS];
+  const void* g[MT_MAX_TENSORS];
+  int size[MT_MAX_TENSORS];
+  int ntensors;
+};
+
+template <typename grad_t>
+__global__ void multi_tensor_sqnorm_kernel(MTNormList tl,
+                                           float* __restrict__ partials,
+                                           int chunk_base, int total_chunks) {
+  __shared__ float lds[32];
+  // 16 bytes of gradient per load: 4 floats or 8 bf16
+  constexpr int VEC = 16 / sizeof(grad_t);
+  typedef __attribute__((ext_vector_type(VEC))) grad_t gvec_t;
+  int b = blockIdx.x;
+  int t = 0;
+  int chunk = 0;
+  for (; t < tl.ntensors; ++t) {
+    const int nchunks = (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
+    if (b < nchunks) { chunk = b; break; }
+    b -= nchunks;
+  }
+  if (t >= tl.ntensors) return;
+  const int start = chunk * MT_CHUNK;
+  const int end = min(start + MT_CHUNK, tl.size[t]);
+  const float* w = tl.w[t];
+  const grad_t* g = (const grad_t*)tl.g[t];
+  float sw = 0.f, sg = 0.f;
+  int tail = start;   // first element of the scalar loop
+  if ((((size_t)w | (size_t)g) & 15) == 0) {
+    // start is a multiple of MT_CHUNK, so every 16-byte load is aligned
+    tail = start + ((end - start) & ~(VEC - 1));
+    for (int i = start + VEC * threadIdx.x; i < tail; i += VEC * blockDim.x) {
+      float wv[VEC];
+      #pragma unroll
+      for (int e = 0; e < VEC; e += 4)
+        *(float4*)(wv + e) = *(const float4*)(w + i + e);
+      const gvec_t gv = *(const gvec_t*)(g + i);
+      #pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        const float gf = (float)gv[e];
+        sw += wv[e] * wv[e];
+        sg += gf * gf;
+      }
+    }
+  }
+  for (int i = tail + threadIdx.x; i < end; i += blockDim.x) {
+    const float wf = w[i];
+    const float gf = (float)g[i];
+    sw += wf * wf;
+    sg += gf * gf;
+  }
+  sw = block_reduce_sum(sw, lds);
+  __syncthreads();
+  sg = block_reduce_sum(sg, lds);
+  if (threadIdx.x == 0) {
+    partials[chunk_base + blockIdx.x] = sw;
+    partials[total_chunks + chunk_base + blockIdx.x] = sg;
+  }
+}
+
+// Block t sums the partials of tensor t of this launch: strided over the
+// block's threads, then block_reduce_sum.
+__global__ void multi_tensor_sqnorm_fold_kernel(MTNormList tl,
+                                                const float* __restrict__ partials,
+                                                float* __restrict__ sq,
+                                                int chunk_base, int total_chunks,
+                                                int tensor_base, int n) {
+  __shared__ float lds[32];
+  const int t = blockIdx.x;
+  if (t >= tl.ntensors) return;
+  int off = chunk_base;
+  for (int u = 0; u < t; ++u) off += (tl.size[u] + MT_CHUNK - 1) / MT_CHUNK;
+  const int nchunks = (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
+  float sw = 0.f, sg = 0.f;
+  for (int j = threadIdx.x; j < nchunks; j += blockDim.x) {
+    sw += partials[off + j];
+    sg += partials[total_chunks + off + j];
+  }
+  sw = block_reduce_sum(sw, lds);
+  __syncthreads();
+  sg = block_reduce_sum(sg, lds);
+  if (threadIdx.x == 0) {
+    sq[tensor_base + t] = sw;
+    sq[n + tensor_base + t] = sg;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// sq -> the coefficients of the scaled SGD step, one block:
+//   norm     = sqrt(sum_t sq_g[t])                 (t in index order)
+//   c        = min(1, max_norm / (norm + CLIP_EPS))   1 when max_norm <= 0
+//   ratio[t] = eta*|w_t| / (c*|g_t| + wd*|w_t| + LARS_EPS)
+// ratio[t] is 1 when LARS is off, when t is flagged excluded, and when |w_t|
+// or |g_t| is 0. c is torch.nn.utils.clip_grad_norm_'s coefficient. The sum
+// covers all n tensors; ratios are written for [lo, hi) only, so that param
+// groups with different settings share one global norm.
+// ---------------------------------------------------------------------------
+constexpr float CLIP_EPS = 1e-6f;
+constexpr float LARS_EPS = 1e-8f;
+
+__global__ void sgd_coeffs_kernel(const float* __restrict__ sq,
+                                  const unsigned char* __restrict__ excluded,
+                                  float* __restrict__ gscale,
+                                  float* __restrict__ ratio,
+                                  float* __restrict__ gnorm,
+                                  int n, int lo, int hi, float max_norm,
+                                  bool lars, float eta, float wd) {
+  __shared__ float c_sh;
+  if (threadIdx.x == 0) {
+    float total = 0.f;
+    for (int t = 0; t < n; ++t) total += sq[n + t];
+    const float norm = sqrtf(total);
+    const float c = max_norm > 0.f
+        ? fminf(1.f, max_norm / (norm + CLIP_EPS)) : 1.f;
+    gscale[0] = c;
+    gnorm[0] = norm;
+    c_sh = c;
+  }
+  __syncthreads();
+  const float c = c_sh;
+  for (int t = lo + threadIdx.x; t < hi; t += blockDim.x) {
+    float r = 1.f;
+    if (lars && !excluded[t]) {
+      const float wn = sqrtf(sq[t]);
+      const float gn = sqrtf(sq[n + t]);
+      if (wn > 0.f && gn > 0.f) r = eta * wn / (c * gn + wd * wn + LARS_EPS);
+    }
+    ratio[t] = r;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// multi_tensor_sgd_kernel with the gradient clipped and the update scaled per
+// tensor, both by coefficients read from device memory (sgd_coeffs_kernel):
+//   d = ratio[t] * (c*g + wd*p) ; m <- mu*m + d ; p <- p - lr*m
+// g is not modified. Shadows, vector/scalar split and the one-expression rule
+// are those of multi_tensor_sgd_kernel.
+// ---------------------------------------------------------------------------
+__global__ void multi_tensor_sgd_scaled_kernel(MTTensorList tl, float lr,
+                                               float mu, float wd,
+                                               bool has_momentum,
+                                               const float* __restrict__ gscale,
+                                               const float* __restrict__ ratio) {
+  int b = blockIdx.x;
+  int t = 0;
+  int chunk = 0;
+  for (; t < tl.ntensors; ++t) {
+    const int nchunks = (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
+    if (b < nchunks) { chunk = b; break; }
+    b -= nchunks;
+  }
+  if (t >= tl.ntensors) return;
+  const int start = chunk * MT_CHUNK;
+  const int end = min(start + MT_CHUNK, tl.size[t]);
+  const float c = gscale[0];
+  const float rt = ratio[t];
+  float* p = tl.p[t];
+  float* g = tl.g[t];
+  float* m = has_momentum ? tl.m[t] : nullptr;
+  void* w16 = tl.w16[t];
+  const bool half = tl.w16_half[t];
+  const bool vec = (((size_t)p | (size_t)g | (size_t)m) & 15) == 0 &&
+                   ((size_t)w16 & 7) == 0;
+  int tail = start;   // first element of the scalar loop
+  if (vec) {
+    tail = start + ((end - start) & ~3);
+    for (int i = start + 4 * threadIdx.x; i < tail; i += 4 * blockDim.x) {
+      float pv[4], gv[4], mv[4];
+      *(float4*)pv = *(const float4*)(p + i);
+      *(float4*)gv = *(const float4*)(g + i);
+      if (has_momentum) *(float4*)mv = *(const float4*)(m + i);
+      #pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float grad = rt * (c * gv[e] + wd * pv[e]);
+        if (has_momentum) {
+          grad = mu * mv[e] + grad;
+          mv[e] = grad;
+        }
+        pv[e] -= lr * grad;
+      }
+      if (has_momentum) *(float4*)(m + i) = *(float4*)mv;
+      *(float4*)(p + i) = *(float4*)pv;
+      if (w16 != nullptr) {
+        if (half) {
+          mthalfx4 o;
+          #pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = (_Float16)pv[e];
+          *(mthalfx4*)((_Float16*)w16 + i) = o;
+        } else {
+          mtbf16x4 o;
+          #pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = (__bf16)pv[e];
+          *(mtbf16x4*)((__bf16*)w16 + i) = o;
+        }
+      }
+    }
+  }
+  for (int i = tail + threadIdx.x; i < end; i += blockDim.x) {
+    float grad = rt * (c * g[i] + wd * p[i]);
+    if (has_momentum) {
+      grad = mu * m[i] + grad;
+      m[i] = grad;
+    }
+    const float pn = p[i] - lr * grad;
+    p[i] = pn;
+    if (w16 != nullptr) {
+      if (half) ((_Float16*)w16)[i] = (_Float16)pn;
+      else ((__bf16*)w16)[i] = (__bf16)pn;
+    }
+  }
+}
+
+// multi_tensor_sgd_o2_kernel with the same two coefficients:
+//   d = ratio[t] * (c*g + wd*master) ; m <- mu*m + d ;
+//   master <- master - lr*m ; p <- (bf16)master
+__global__ void multi_tensor_sgd_o2_scaled_kernel(MTMixedList tl, float lr,
+                                                  float mu, float wd,
+                                                  bool has_momentum,
+                                                  const float* __restrict__ gscale,
+                                                  const float* __restrict__ ratio) {
+  int b = blockIdx.x;
+  int t = 0;
+  int chunk = 0;
+  for (; t < tl.ntensors; ++t) {
+    const int nchunks = (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
+    if (b < nchunks) { chunk = b; break; }
+    b -= nchunks;
+  }
+  if (t >= tl.ntensors) return;
+  const int start = chunk * MT_CHUNK;
+  const int end = min(start + MT_CHUNK, tl.size[t]);
+  const float c = gscale[0];
+  const float rt = ratio[t];
+  __bf16* p = tl.p[t];
+  const __bf16* g = tl.g[t];
+  float* w = tl.w[t];
+  float* m = has_momentum ? tl.m[t] : nullptr;
+  for (int i = start + threadIdx.x; i < end; i += blockDim.x) {
+    float grad = rt * (c * (float)g[i] + wd * w[i]);
+    if (has_momentum) {
+      grad = mu * m[i] + grad;
+      m[i] = grad;
+    }
+    const float nw = w[i] - lr * grad;
+    w[i] = nw;
+    p[i] = (__bf16)nw;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Multi-tensor unscale + inf/nan check (fp16 loss-scaler backward pass).
 // ---------------------------------------------------------------------------
 struct MTGradList {
@@ -1968,13 +2232,19 @@ at::Tensor xent_mix_bwd(at::Tensor logits, at::Tensor target_a,
   return dx;
 }
 
-void multi_tensor_sgd(std::vector<at::Tensor> params,
-                      std::vector<at::Tensor> grads,
-                      std::vector<at::Tensor> bufs,
-                      double lr, double momentum, double weight_decay,
-                      std::vector<c10::optional<at::Tensor>> w16s) {
+// gscale/ratio null: the plain kernel. Otherwise the scaled one, with
+// ratio[i] the coefficient of params[i].
+static void multi_tensor_sgd_impl(std::vector<at::Tensor>& params,
+                                  std::vector<at::Tensor>& grads,
+                                  std::vector<at::Tensor>& bufs,
+                                  double lr, double momentum,
+                                  double weight_decay,
+                                  std::vector<c10::optional<at::Tensor>>& w16s,
+                                  const float* gscale, const float* ratio) {
   const bool has_momentum = !bufs.empty();
   TORCH_CHECK(params.size() == grads.size());
+  TORCH_CHECK(!has_momentum || bufs.size() == params.size(),
+              "multi_tensor_sgd: one momentum buffer per param");
   TORCH_CHECK(w16s.empty() || w16s.size() == params.size(),
               "multi_tensor_sgd: one w16 entry (or None) per param");
   auto stream = cur_stream();
@@ -2010,20 +2280,64 @@ void multi_tensor_sgd(std::vector<at::Tensor> params,
       nblocks += (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
     }
     tl.ntensors = t;
-    hipLaunchKernelGGL(multi_tensor_sgd_kernel, dim3(nblocks), dim3(256), 0,
-                       stream, tl, (float)lr, (float)momentum,
-                       (float)weight_decay, has_momentum);
+    if (gscale == nullptr) {
+      hipLaunchKernelGGL(multi_tensor_sgd_kernel, dim3(nblocks), dim3(256), 0,
+                         stream, tl, (float)lr, (float)momentum,
+                         (float)weight_decay, has_momentum);
+    } else {
+      hipLaunchKernelGGL(multi_tensor_sgd_scaled_kernel, dim3(nblocks),
+                         dim3(256), 0, stream, tl, (float)lr, (float)momentum,
+                         (float)weight_decay, has_momentum, gscale,
+                         ratio + (i - t));
+    }
   }
 }
 
-void multi_tensor_sgd_o2(std::vector<at::Tensor> params,
-                         std::vector<at::Tensor> grads,
-                         std::vector<at::Tensor> masters,
-                         std::vector<at::Tensor> bufs,
-                         double lr, double momentum, double weight_decay) {
+void multi_tensor_sgd(std::vector<at::Tensor> params,
+                      std::vector<at::Tensor> grads,
+                      std::vector<at::Tensor> bufs,
+                      double lr, double momentum, double weight_decay,
+                      std::vector<c10::optional<at::Tensor>> w16s) {
+  multi_tensor_sgd_impl(params, grads, bufs, lr, momentum, weight_decay, w16s,
+                        nullptr, nullptr);
+}
+
+// The two device coefficients of the scaled kernels: gscale [1], ratio [n].
+static void check_coeffs(const at::Tensor& gscale, const at::Tensor& ratio,
+                         size_t n, const at::Tensor& like) {
+  TORCH_CHECK(gscale.is_cuda() && gscale.scalar_type() == at::kFloat &&
+              gscale.numel() == 1 && gscale.device() == like.device(),
+              "gscale must be one float32 on the params' device");
+  TORCH_CHECK(ratio.is_cuda() && ratio.scalar_type() == at::kFloat &&
+              ratio.is_contiguous() && (size_t)ratio.numel() == n &&
+              ratio.device() == like.device(),
+              "ratio must be a contiguous float32 [n], one per param");
+}
+
+void multi_tensor_sgd_scaled(std::vector<at::Tensor> params,
+                             std::vector<at::Tensor> grads,
+                             std::vector<at::Tensor> bufs,
+                             double lr, double momentum, double weight_decay,
+                             at::Tensor gscale, at::Tensor ratio,
+                             std::vector<c10::optional<at::Tensor>> w16s) {
+  if (params.empty()) return;
+  check_coeffs(gscale, ratio, params.size(), params[0]);
+  multi_tensor_sgd_impl(params, grads, bufs, lr, momentum, weight_decay, w16s,
+                        gscale.data_ptr<float>(), ratio.data_ptr<float>());
+}
+
+static void multi_tensor_sgd_o2_impl(std::vector<at::Tensor>& params,
+                                     std::vector<at::Tensor>& grads,
+                                     std::vector<at::Tensor>& masters,
+                                     std::vector<at::Tensor>& bufs,
+                                     double lr, double momentum,
+                                     double weight_decay,
+                                     const float* gscale, const float* ratio) {
   const bool has_momentum = !bufs.empty();
   TORCH_CHECK(params.size() == grads.size() &&
               params.size() == masters.size());
+  TORCH_CHECK(!has_momentum || bufs.size() == params.size(),
+              "multi_tensor_sgd_o2: one momentum buffer per param");
   auto stream = cur_stream();
   size_t i = 0;
   while (i < params.size()) {
@@ -2049,10 +2363,137 @@ void multi_tensor_sgd_o2(std::vector<at::Tensor> params,
       nblocks += (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
     }
     tl.ntensors = t;
-    hipLaunchKernelGGL(multi_tensor_sgd_o2_kernel, dim3(nblocks), dim3(256),
-                       0, stream, tl, (float)lr, (float)momentum,
-                       (float)weight_decay, has_momentum);
+    if (gscale == nullptr) {
+      hipLaunchKernelGGL(multi_tensor_sgd_o2_kernel, dim3(nblocks), dim3(256),
+                         0, stream, tl, (float)lr, (float)momentum,
+                         (float)weight_decay, has_momentum);
+    } else {
+      hipLaunchKernelGGL(multi_tensor_sgd_o2_scaled_kernel, dim3(nblocks),
+                         dim3(256), 0, stream, tl, (float)lr, (float)momentum,
+                         (float)weight_decay, has_momentum, gscale,
+                         ratio + (i - t));
+    }
   }
+}
+
+void multi_tensor_sgd_o2(std::vector<at::Tensor> params,
+                         std::vector<at::Tensor> grads,
+                         std::vector<at::Tensor> masters,
+                         std::vector<at::Tensor> bufs,
+                         double lr, double momentum, double weight_decay) {
+  multi_tensor_sgd_o2_impl(params, grads, masters, bufs, lr, momentum,
+                           weight_decay, nullptr, nullptr);
+}
+
+void multi_tensor_sgd_o2_scaled(std::vector<at::Tensor> params,
+                                std::vector<at::Tensor> grads,
+                                std::vector<at::Tensor> masters,
+                                std::vector<at::Tensor> bufs,
+                                double lr, double momentum,
+                                double weight_decay,
+                                at::Tensor gscale, at::Tensor ratio) {
+  if (params.empty()) return;
+  check_coeffs(gscale, ratio, params.size(), params[0]);
+  multi_tensor_sgd_o2_impl(params, grads, masters, bufs, lr, momentum,
+                           weight_decay, gscale.data_ptr<float>(),
+                           ratio.data_ptr<float>());
+}
+
+// sq[0][i] <- sum w_i^2, sq[1][i] <- sum g_i^2 for every tensor, through
+// `partials` ([2][>= total chunks]). Both buffers belong to the caller and
+// nothing is allocated here. A launch holds gradients of one dtype, so the
+// list is cut where the dtype changes as well as at MT_MAX_TENSORS.
+void multi_tensor_sqnorm(std::vector<at::Tensor> ws,
+                         std::vector<at::Tensor> gs,
+                         at::Tensor partials, at::Tensor sq) {
+  TORCH_CHECK(ws.size() == gs.size(), "multi_tensor_sqnorm: one g per w");
+  if (ws.empty()) return;
+  const int n = (int)ws.size();
+  long total_chunks = 0;
+  for (auto& w : ws) total_chunks += (w.numel() + MT_CHUNK - 1) / MT_CHUNK;
+  auto dev_f32 = [&](const at::Tensor& x) {
+    return x.is_cuda() && x.scalar_type() == at::kFloat &&
+           x.is_contiguous() && x.device() == ws[0].device();
+  };
+  TORCH_CHECK(dev_f32(partials) && partials.dim() == 2 &&
+              partials.size(0) == 2 && partials.size(1) >= total_chunks,
+              "multi_tensor_sqnorm: partials must be float32 [2][>= ",
+              total_chunks, "]");
+  TORCH_CHECK(dev_f32(sq) && sq.dim() == 2 && sq.size(0) == 2 &&
+              sq.size(1) == n,
+              "multi_tensor_sqnorm: sq must be float32 [2][", n, "]");
+  const int pstride = (int)partials.size(1);
+  auto stream = cur_stream();
+  int chunk_base = 0;
+  size_t i = 0;
+  while (i < ws.size()) {
+    MTNormList tl;
+    const auto gdtype = gs[i].scalar_type();
+    const int tensor_base = (int)i;
+    int nblocks = 0;
+    int t = 0;
+    for (; t < MT_MAX_TENSORS && i < ws.size() &&
+           gs[i].scalar_type() == gdtype; ++t, ++i) {
+      auto& w = ws[i];
+      auto& g = gs[i];
+      TORCH_CHECK(w.is_cuda() && w.is_non_overlapping_and_dense() &&
+                  w.scalar_type() == at::kFloat &&
+                  w.device() == ws[0].device(),
+                  "multi_tensor_sqnorm expects dense fp32 weights");
+      TORCH_CHECK(g.is_cuda() && g.is_non_overlapping_and_dense() &&
+                  g.numel() == w.numel() && g.device() == w.device() &&
+                  (gdtype == at::kFloat || gdtype == at::kBFloat16),
+                  "multi_tensor_sqnorm expects dense fp32 or bf16 grads of "
+                  "the weights' sizes");
+      tl.w[t] = w.data_ptr<float>();
+      tl.g[t] = g.data_ptr();
+      tl.size[t] = (int)w.numel();
+      nblocks += (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
+    }
+    tl.ntensors = t;
+    if (nblocks > 0) {
+      if (gdtype == at::kFloat) {
+        hipLaunchKernelGGL(multi_tensor_sqnorm_kernel<float>, dim3(nblocks),
+                           dim3(256), 0, stream, tl,
+                           partials.data_ptr<float>(), chunk_base, pstride);
+      } else {
+        hipLaunchKernelGGL(multi_tensor_sqnorm_kernel<__bf16>, dim3(nblocks),
+                           dim3(256), 0, stream, tl,
+                           partials.data_ptr<float>(), chunk_base, pstride);
+      }
+    }
+    hipLaunchKernelGGL(multi_tensor_sqnorm_fold_kernel, dim3(t), dim3(256), 0,
+                       stream, tl, partials.data_ptr<float>(),
+                       sq.data_ptr<float>(), chunk_base, pstride, tensor_base,
+                       n);
+    chunk_base += nblocks;
+  }
+}
+
+// sq ([2][n], multi_tensor_sqnorm) -> gscale[0] = clip coefficient, gnorm =
+// pre-clip global gradient norm, ratio[lo:hi] = LARS trust ratios.
+void sgd_coeffs(at::Tensor sq, at::Tensor excluded, at::Tensor gscale,
+                at::Tensor ratio, at::Tensor gnorm, double max_norm, bool lars,
+                double eta, double weight_decay, int64_t lo, int64_t hi) {
+  TORCH_CHECK(sq.is_cuda() && sq.scalar_type() == at::kFloat &&
+              sq.is_contiguous() && sq.dim() == 2 && sq.size(0) == 2,
+              "sgd_coeffs: sq must be a contiguous float32 [2][n]");
+  const int64_t n = sq.size(1);
+  if (hi < 0) hi = n;
+  TORCH_CHECK(0 <= lo && lo <= hi && hi <= n, "sgd_coeffs: bad range");
+  TORCH_CHECK(excluded.is_cuda() && excluded.scalar_type() == at::kByte &&
+              excluded.is_contiguous() && excluded.numel() == n &&
+              excluded.device() == sq.device(),
+              "sgd_coeffs: excluded must be uint8 [n]");
+  check_coeffs(gscale, ratio, (size_t)n, sq);
+  TORCH_CHECK(gnorm.is_cuda() && gnorm.scalar_type() == at::kFloat &&
+              gnorm.numel() == 1 && gnorm.device() == sq.device(),
+              "sgd_coeffs: gnorm must be one float32");
+  hipLaunchKernelGGL(sgd_coeffs_kernel, dim3(1), dim3(256), 0, cur_stream(),
+                     sq.data_ptr<float>(), excluded.data_ptr<unsigned char>(),
+                     gscale.data_ptr<float>(), ratio.data_ptr<float>(),
+                     gnorm.data_ptr<float>(), (int)n, (int)lo, (int)hi,
+                     (float)max_norm, lars, (float)eta, (float)weight_decay);
 }
 
 at::Tensor multi_tensor_unscale(std::vector<at::Tensor> grads, double inv_scale) {
@@ -2291,6 +2732,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w16s") = std::vector<c10::optional<at::Tensor>>());
   m.def("multi_tensor_sgd_o2", &multi_tensor_sgd_o2,
         "fused SGD with bf16 params/grads + fp32 master (apex O2)");
+  m.def("multi_tensor_sqnorm", &multi_tensor_sqnorm,
+        "per-tensor sums of squares of w (fp32) and g (fp32|bf16) -> sq "
+        "[2][n] through partials [2][>= chunks]; fixed order, no atomics",
+        py::arg("ws"), py::arg("gs"), py::arg("partials"), py::arg("sq"));
+  m.def("sgd_coeffs", &sgd_coeffs,
+        "sq -> gscale[0] = min(1, max_norm/(|g| + 1e-6)) (1 when max_norm <= "
+        "0), gnorm = |g|, ratio[lo:hi] = LARS trust ratios (1 when lars is "
+        "off, excluded, or a norm is 0)",
+        py::arg("sq"), py::arg("excluded"), py::arg("gscale"),
+        py::arg("ratio"), py::arg("gnorm"), py::arg("max_norm"),
+        py::arg("lars"), py::arg("eta"), py::arg("weight_decay"),
+        py::arg("lo") = 0, py::arg("hi") = -1);
+  m.def("multi_tensor_sgd_scaled", &multi_tensor_sgd_scaled,
+        "multi_tensor_sgd with d = ratio[t]*(gscale[0]*g + wd*p) read from "
+        "device memory; g is not modified",
+        py::arg("params"), py::arg("grads"), py::arg("bufs"), py::arg("lr"),
+        py::arg("momentum"), py::arg("weight_decay"), py::arg("gscale"),
+        py::arg("ratio"),
+        py::arg("w16s") = std::vector<c10::optional<at::Tensor>>());
+  m.def("multi_tensor_sgd_o2_scaled", &multi_tensor_sgd_o2_scaled,
+        "multi_tensor_sgd_o2 with d = ratio[t]*(gscale[0]*g + wd*master)",
+        py::arg("params"), py::arg("grads"), py::arg("masters"),
+        py::arg("bufs"), py::arg("lr"), py::arg("momentum"),
+        py::arg("weight_decay"), py::arg("gscale"), py::arg("ratio"));
   m.def("multi_tensor_unscale", &multi_tensor_unscale,
         "multi-tensor grad unscale + inf/nan check");
   m.def("gap_fwd", &gap_fwd, "global average pool forward (NCHW/NHWC)");

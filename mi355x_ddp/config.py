@@ -78,6 +78,12 @@ class TrainConfig:
     label_smoothing: float = 0.0
     cutmix_alpha: float = 0.0
     cutmix_prob: float = 0.5
+    # optimiser features beyond the reference's recipe (ops/sgd.py): LARS
+    # trust ratios for tensors with ndim > 1, and clipping by the global
+    # gradient norm inside the fused step (0 = off)
+    lars: bool = False
+    lars_eta: float = 1e-3
+    clip_grad_norm: float = 0.0
 
     # native kernels
     native_ops: bool = True           # HIP kernels when extension present; fail loudly on GPU if absent
@@ -112,6 +118,11 @@ class TrainConfig:
         if not 0.0 <= self.label_smoothing < 1.0:
             raise ValueError("label_smoothing must be in [0, 1), got "
                              f"{self.label_smoothing}")
+        if self.lars_eta <= 0:
+            raise ValueError(f"lars_eta must be > 0, got {self.lars_eta}")
+        if self.clip_grad_norm < 0:
+            raise ValueError("clip_grad_norm must be >= 0 (0 turns clipping "
+                             f"off), got {self.clip_grad_norm}")
 
     def per_rank_batch(self, world_size: int) -> int:
         return max(1, self.batch_size // max(1, world_size))
@@ -180,6 +191,14 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                         "(needs --device_data)")
     p.add_argument("--cutmix_prob", default=None, type=float,
                    help="probability that a sample is mixed (default 0.5)")
+    p.add_argument("--lars", action="store_true",
+                   help="layer-wise adaptive rate scaling in the fused SGD "
+                        "step (tensors with ndim <= 1 are not adapted)")
+    p.add_argument("--lars_eta", default=None, type=float,
+                   help="LARS trust coefficient (default 1e-3)")
+    p.add_argument("--clip_grad_norm", default=None, type=float,
+                   help="clip gradients to this global L2 norm inside the "
+                        "fused SGD step; 0 = off")
     return p
 
 
@@ -221,7 +240,10 @@ def config_from_args(args: argparse.Namespace, **overrides) -> TrainConfig:
         kw["device_data"] = True
     if getattr(args, "hflip", False):
         kw["hflip"] = True
-    for name in ("label_smoothing", "cutmix_alpha", "cutmix_prob"):
+    if getattr(args, "lars", False):
+        kw["lars"] = True
+    for name in ("label_smoothing", "cutmix_alpha", "cutmix_prob",
+                 "lars_eta", "clip_grad_norm"):
         if getattr(args, name, None) is not None:
             kw[name] = getattr(args, name)
     kw.update(overrides)

@@ -133,8 +133,14 @@ def train_one_epoch(model, loader, criterion, optimizer, epoch: int,
                       f"Loss {float(reduced):.4f}\tTime {step_time.val:.3f}\t"
                       f"LR {lr:.5f}", flush=True)
                 if sink is not None:
+                    extra = {}
+                    gn = optimizer.grad_norm() \
+                        if hasattr(optimizer, "grad_norm") else None
+                    if gn is not None:
+                        extra["grad_norm"] = float(gn)
                     sink.log(kind="train", epoch=epoch, step=step,
-                             loss=float(reduced), lr=lr, step_time=step_time.val)
+                             loss=float(reduced), lr=lr,
+                             step_time=step_time.val, **extra)
     # leave no deferral active outside the loop (direct bn_relu callers,
     # eval paths) and no pending bumps unapplied on early exits
     flush_num_batches_tracked()

@@ -82,7 +82,9 @@ def build_training(cfg: TrainConfig, device: torch.device, world_size: int,
                                bucket_cap_mb=cfg.bucket_cap_mb)
     criterion = SoftmaxCrossEntropy(cfg.label_smoothing).to(device)
     optimizer = FusedSGD(model.parameters(), lr=cfg.lr, momentum=cfg.momentum,
-                         weight_decay=cfg.weight_decay)
+                         weight_decay=cfg.weight_decay, lars=cfg.lars,
+                         lars_eta=cfg.lars_eta,
+                         clip_grad_norm=cfg.clip_grad_norm)
     scheduler = build_scheduler(optimizer, cfg)
     scaler = build_scaler(cfg.amp)
     return model, criterion, optimizer, scheduler, scaler

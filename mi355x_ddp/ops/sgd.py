@@ -27,6 +27,29 @@ shadow itself — the SGD kernel stores p_new rounded to the shadow's dtype
 into `w16` next to `p` (per tensor: one step may carry bf16 and fp16
 shadows), and one batched `multi_tensor_build_wT` launch rotates every `w16`
 into its `wT` — or marks it stale. Never neither.
+
+LARS and clipping by the global gradient norm (``lars=True``,
+``clip_grad_norm=x``; both off by default, and then the step is exactly the
+one above). With w the fp32 weight (the parameter, or the O2 master), over the
+T tensors that are stepped:
+
+    norm    = sqrt(sum_t |g_t|^2)                       the pre-clip global norm
+    c       = min(1, x / (norm + 1e-6))                 1 when clipping is off
+    ratio_t = eta*|w_t| / (c*|g_t| + wd*|w_t| + 1e-8)   1 when LARS is off
+    d       = ratio_t * (c*g + wd*w) ; m <- mu*m + d ; w <- w - lr*m
+
+c is ``torch.nn.utils.clip_grad_norm_``'s coefficient, but the gradient
+tensors are NOT modified: clipping happens inside the update. ratio_t is 1 for
+tensors with ``ndim <= 1`` (BatchNorm affine, biases; their weight decay stays
+as the group says) and when |w_t| or |g_t| is 0. Parameters without a gradient
+are skipped and do not enter the norm. On the native path the norms, c and the
+ratios are computed on the device (`multi_tensor_sqnorm`, `sgd_coeffs`: fixed
+summation order, no atomics) into buffers that the optimizer keeps, and the
+update kernels read them there: after the first step a step does no host
+sync, no host-to-device copy and no allocation, so it captures into a
+hipGraph. The norm is global over all param groups; max_norm, eta and wd are
+each group's own. The effect of either feature on accuracy has not been
+measured in this project.
 """
 from __future__ import annotations
 
@@ -37,12 +60,88 @@ import torch
 from . import _backend
 from .conv import WeightShadow, shadow_of, weight_shadows_wanted
 
+LARS_EPS = 1e-8   # in the trust ratio's denominator (csrc: LARS_EPS)
+CLIP_EPS = 1e-6   # torch.nn.utils.clip_grad_norm_'s (csrc: CLIP_EPS)
+_MT_CHUNK = 1 << 13   # csrc: MT_CHUNK, elements per block
+
+
+class _NormBuffers:
+    """Device buffers of the scaled step, kept while the list of stepped
+    tensors is unchanged."""
+
+    def __init__(self, key, ws: List[torch.Tensor], excluded: List[bool],
+                 ngroups: int):
+        dev = ws[0].device
+        chunks = sum((w.numel() + _MT_CHUNK - 1) // _MT_CHUNK for w in ws)
+        n = len(ws)
+        self.key = key
+        self.partials = torch.empty(2, max(chunks, 1), device=dev)
+        self.sq = torch.zeros(2, n, device=dev)
+        self.gscale = torch.ones(ngroups, device=dev)
+        self.ratio = torch.ones(n, device=dev)
+        self.gnorm = torch.zeros((), device=dev)
+        self.excluded = torch.tensor(excluded, dtype=torch.uint8).to(dev)
+
+
+def _group_scaled(group) -> bool:
+    return bool(group.get("lars", False)) or \
+        group.get("clip_grad_norm", 0.0) > 0
+
 
 class FusedSGD(torch.optim.Optimizer):
     def __init__(self, params, lr: float, momentum: float = 0.0,
-                 weight_decay: float = 0.0):
-        defaults = dict(lr=lr, momentum=momentum, weight_decay=weight_decay)
+                 weight_decay: float = 0.0, lars: bool = False,
+                 lars_eta: float = 1e-3, clip_grad_norm: float = 0.0):
+        if lars_eta <= 0:
+            raise ValueError(f"lars_eta must be > 0, got {lars_eta}")
+        if clip_grad_norm < 0:
+            raise ValueError("clip_grad_norm must be >= 0 (0 turns clipping "
+                             f"off), got {clip_grad_norm}")
+        defaults = dict(lr=lr, momentum=momentum, weight_decay=weight_decay,
+                        lars=bool(lars), lars_eta=lars_eta,
+                        clip_grad_norm=clip_grad_norm)
         super().__init__(params, defaults)
+        self._norm: Optional[_NormBuffers] = None
+        self._grad_norm: Optional[torch.Tensor] = None
+
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """0-dim tensor on the parameters' device: the global gradient norm of
+        the last step, before clipping. None when LARS and clipping are both
+        off (and before the first step). Reading it is a host sync."""
+        if not any(_group_scaled(g) for g in self.param_groups):
+            return None
+        return getattr(self, "_grad_norm", None)
+
+    def _gather(self, group):
+        """The group's tensors that have a gradient, split into the fp32 and
+        the bf16 (O2) path; creates masters and momentum buffers."""
+        p32, g32, m32, s32 = [], [], [], []
+        p16, g16, w16, m16 = [], [], [], []
+        momentum = group["momentum"]
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            state = self.state[p]
+            if p.dtype == torch.bfloat16:
+                if "master" not in state:
+                    state["master"] = p.detach().float()
+                if momentum != 0 and "momentum_buffer" not in state:
+                    state["momentum_buffer"] = torch.zeros_like(
+                        state["master"])
+                p16.append(p)
+                g16.append(p.grad)
+                w16.append(state["master"])
+                if momentum != 0:
+                    m16.append(state["momentum_buffer"])
+            else:
+                if momentum != 0 and "momentum_buffer" not in state:
+                    state["momentum_buffer"] = torch.zeros_like(p)
+                p32.append(p)
+                g32.append(p.grad)
+                s32.append(shadow_of(p))
+                if momentum != 0:
+                    m32.append(state["momentum_buffer"])
+        return p32, g32, m32, s32, p16, g16, w16, m16
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -50,33 +149,12 @@ class FusedSGD(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if any(_group_scaled(g) for g in self.param_groups):
+            self._step_scaled()
+            return loss
         for group in self.param_groups:
-            p32, g32, m32, s32 = [], [], [], []
-            p16, g16, w16, m16 = [], [], [], []
+            p32, g32, m32, s32, p16, g16, w16, m16 = self._gather(group)
             momentum = group["momentum"]
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                state = self.state[p]
-                if p.dtype == torch.bfloat16:
-                    if "master" not in state:
-                        state["master"] = p.detach().float()
-                    if momentum != 0 and "momentum_buffer" not in state:
-                        state["momentum_buffer"] = torch.zeros_like(
-                            state["master"])
-                    p16.append(p)
-                    g16.append(p.grad)
-                    w16.append(state["master"])
-                    if momentum != 0:
-                        m16.append(state["momentum_buffer"])
-                else:
-                    if momentum != 0 and "momentum_buffer" not in state:
-                        state["momentum_buffer"] = torch.zeros_like(p)
-                    p32.append(p)
-                    g32.append(p.grad)
-                    s32.append(shadow_of(p))
-                    if momentum != 0:
-                        m32.append(state["momentum_buffer"])
             if p32:
                 fused_sgd_step(p32, g32, m32 if momentum != 0 else None,
                                lr=group["lr"], momentum=momentum,
@@ -89,14 +167,100 @@ class FusedSGD(torch.optim.Optimizer):
                                   weight_decay=group["weight_decay"])
         return loss
 
+    def _step_scaled(self) -> None:
+        """The step with LARS and/or clipping on in at least one group."""
+        gathered = [self._gather(g) for g in self.param_groups]
+        # the order of the norm's tensor list: group by group, a group's fp32
+        # tensors before its bf16 ones, so each path's ratios are one slice
+        ws, gs, excluded, ranges = [], [], [], []
+        for p32, g32, _, _, p16, g16, w16, _ in gathered:
+            lo = len(ws)
+            ws += p32 + w16
+            gs += g32 + g16
+            excluded += [p.ndim <= 1 for p in p32 + p16]
+            ranges.append((lo, lo + len(p32), len(ws)))
+        if not ws:
+            return
+        native = _backend.native_enabled(ws[0])
+        if native:
+            # all that the buffers' sizes and contents depend on
+            key = (tuple(w.numel() for w in ws), tuple(excluded),
+                   len(self.param_groups), ws[0].device)
+            nb = getattr(self, "_norm", None)
+            if nb is None or nb.key != key:
+                nb = self._norm = _NormBuffers(key, ws, excluded,
+                                               len(self.param_groups))
+            _backend.C().multi_tensor_sqnorm(ws, gs, nb.partials, nb.sq)
+            self._grad_norm = nb.gnorm
+        else:
+            sq_w = torch.stack([w.float().pow(2).sum() for w in ws])
+            sq_g = torch.stack([g.float().pow(2).sum() for g in gs])
+        for gi, (group, got, (lo, mid, hi)) in enumerate(
+                zip(self.param_groups, gathered, ranges)):
+            if lo == hi:
+                continue
+            p32, g32, m32, s32, p16, g16, w16, m16 = got
+            momentum = group["momentum"]
+            wd = group["weight_decay"]
+            max_norm = group.get("clip_grad_norm", 0.0)
+            lars = bool(group.get("lars", False))
+            eta = group.get("lars_eta", 1e-3)
+            if native:
+                gscale = nb.gscale[gi:gi + 1]
+                ratio = nb.ratio
+                _backend.C().sgd_coeffs(nb.sq, nb.excluded, gscale, ratio,
+                                        nb.gnorm, max_norm, lars, eta, wd,
+                                        lo, hi)
+            else:
+                gscale, ratio, self._grad_norm = sgd_coeffs_torch(
+                    sq_w, sq_g, excluded, max_norm, lars, eta, wd)
+            if p32:
+                fused_sgd_step(p32, g32, m32 if momentum != 0 else None,
+                               lr=group["lr"], momentum=momentum,
+                               weight_decay=wd, shadows=s32,
+                               gscale=gscale, ratio=ratio[lo:mid])
+            if p16:
+                fused_sgd_o2_step(p16, g16, w16,
+                                  m16 if momentum != 0 else None,
+                                  lr=group["lr"], momentum=momentum,
+                                  weight_decay=wd,
+                                  gscale=gscale, ratio=ratio[mid:hi])
+
+
+def sgd_coeffs_torch(sq_w: torch.Tensor, sq_g: torch.Tensor,
+                     excluded: List[bool], max_norm: float, lars: bool,
+                     eta: float, weight_decay: float):
+    """The `sgd_coeffs` kernel's math in torch, in its order: per-tensor sums
+    of squares (fp32 [n] each) -> (gscale [1], ratio [n], global norm)."""
+    total = sq_g[0]
+    for t in range(1, sq_g.numel()):   # index order, as the kernel
+        total = total + sq_g[t]
+    norm = total.sqrt()
+    if max_norm > 0:
+        c = (max_norm / (norm + CLIP_EPS)).clamp(max=1.0)
+    else:
+        c = torch.ones_like(norm)
+    ratio = torch.ones_like(sq_w)
+    if lars:
+        wn, gn = sq_w.sqrt(), sq_g.sqrt()
+        adapt = (wn > 0) & (gn > 0) & ~torch.tensor(
+            excluded, dtype=torch.bool, device=sq_w.device)
+        trust = eta * wn / (c * gn + weight_decay * wn + LARS_EPS)
+        ratio = torch.where(adapt, trust, ratio)
+    return c.reshape(1), ratio, norm
+
 
 def fused_sgd_step(params: List[torch.Tensor], grads: List[torch.Tensor],
                    momentum_bufs: Optional[List[torch.Tensor]],
                    lr: float, momentum: float, weight_decay: float,
-                   shadows: Optional[List[Optional[WeightShadow]]] = None
-                   ) -> None:
+                   shadows: Optional[List[Optional[WeightShadow]]] = None,
+                   gscale: Optional[torch.Tensor] = None,
+                   ratio: Optional[torch.Tensor] = None) -> None:
     """`shadows[i]` is params[i]'s WeightShadow or None. Each one is either
-    rewritten with the new weight here (native path) or invalidated."""
+    rewritten with the new weight here (native path) or invalidated.
+
+    With `gscale` ([1]) and `ratio` ([len(params)]) the update is the scaled
+    one, d = ratio[i]*(gscale*g + wd*p); the gradients are not modified."""
     live = []
     for p, sh in zip(params, shadows or ()):
         if sh is None:
@@ -111,9 +275,14 @@ def fused_sgd_step(params: List[torch.Tensor], grads: List[torch.Tensor],
             keep = {id(sh) for _, sh in live}
             w16s = [sh.w16 if sh is not None and id(sh) in keep else None
                     for sh in shadows]
-        _backend.C().multi_tensor_sgd(params, grads,
-                                      momentum_bufs if momentum_bufs is not None else [],
-                                      lr, momentum, weight_decay, w16s)
+        bufs = momentum_bufs if momentum_bufs is not None else []
+        if gscale is None:
+            _backend.C().multi_tensor_sgd(params, grads, bufs,
+                                          lr, momentum, weight_decay, w16s)
+        else:
+            _backend.C().multi_tensor_sgd_scaled(params, grads, bufs,
+                                                 lr, momentum, weight_decay,
+                                                 gscale, ratio, w16s)
         if live:
             _backend.C().multi_tensor_build_wT([sh.w16 for _, sh in live],
                                                [sh.wT for _, sh in live])
@@ -124,7 +293,9 @@ def fused_sgd_step(params: List[torch.Tensor], grads: List[torch.Tensor],
         sh.invalidate()
     # torch fallback, same math (used on CPU and for parity tests)
     for i, (p, g) in enumerate(zip(params, grads)):
-        if weight_decay != 0:
+        if gscale is not None:
+            g = ratio[i] * (gscale[0] * g + weight_decay * p)
+        elif weight_decay != 0:
             g = g.add(p, alpha=weight_decay)
         if momentum_bufs is not None:
             buf = momentum_bufs[i]
@@ -136,17 +307,26 @@ def fused_sgd_step(params: List[torch.Tensor], grads: List[torch.Tensor],
 def fused_sgd_o2_step(params: List[torch.Tensor], grads: List[torch.Tensor],
                       masters: List[torch.Tensor],
                       momentum_bufs: Optional[List[torch.Tensor]],
-                      lr: float, momentum: float, weight_decay: float) -> None:
-    """bf16 params/grads, fp32 master + momentum (apex-O2 update)."""
+                      lr: float, momentum: float, weight_decay: float,
+                      gscale: Optional[torch.Tensor] = None,
+                      ratio: Optional[torch.Tensor] = None) -> None:
+    """bf16 params/grads, fp32 master + momentum (apex-O2 update); scaled as
+    in fused_sgd_step when `gscale` and `ratio` are given."""
     if params and _backend.native_enabled(params[0]):
-        _backend.C().multi_tensor_sgd_o2(
-            params, grads, masters,
-            momentum_bufs if momentum_bufs is not None else [],
-            lr, momentum, weight_decay)
+        bufs = momentum_bufs if momentum_bufs is not None else []
+        if gscale is None:
+            _backend.C().multi_tensor_sgd_o2(
+                params, grads, masters, bufs, lr, momentum, weight_decay)
+        else:
+            _backend.C().multi_tensor_sgd_o2_scaled(
+                params, grads, masters, bufs, lr, momentum, weight_decay,
+                gscale, ratio)
         return
     for i, (p, g, w) in enumerate(zip(params, grads, masters)):
         gf = g.float()
-        if weight_decay != 0:
+        if gscale is not None:
+            gf = ratio[i] * (gscale[0] * gf + weight_decay * w)
+        elif weight_decay != 0:
             gf = gf.add(w, alpha=weight_decay)
         if momentum_bufs is not None:
             buf = momentum_bufs[i]
