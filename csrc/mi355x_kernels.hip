@@ -850,13 +850,62 @@ __global__ void xent_mix_bwd_kernel(const scalar_t* __restrict__ logits,
 }
 
 // ---------------------------------------------------------------------------
-// Multi-tensor SGD with momentum + weight decay (exact torch.optim.SGD math):
-//   m <- mu*m + g + wd*p ; p <- p - lr*m
-// Tensor pointers travel in kernel-arg space (no host->device table copies);
-// each block linear-scans the per-tensor chunk counts to find its tensor.
+// Multi-tensor kernels: one launch works on up to MT_MAX_TENSORS tensors, one
+// 256-thread block per MT_CHUNK elements of each. Tensor pointers travel in
+// kernel-arg space (no host->device table copies); each block linear-scans
+// the per-tensor chunk counts to find its tensor (mt_locate).
 // ---------------------------------------------------------------------------
 constexpr int MT_MAX_TENSORS = 32;
 constexpr int MT_CHUNK = 1 << 13;
+
+template <typename int_t>
+__host__ __device__ constexpr int_t mt_chunks(int_t numel) {
+  return (numel + MT_CHUNK - 1) / MT_CHUNK;
+}
+
+// Tensor t and its elements [start, end) of this block, for any of the list
+// structs below. False when the block is past the launch's last chunk.
+template <typename List>
+__device__ __forceinline__ bool mt_locate(const List& tl, int& t, int& start,
+                                          int& end) {
+  int b = blockIdx.x;
+  for (t = 0; t < tl.ntensors; ++t) {
+    const int nchunks = mt_chunks(tl.size[t]);
+    if (b < nchunks) break;
+    b -= nchunks;
+  }
+  if (t >= tl.ntensors) return false;
+  start = b * MT_CHUNK;
+  end = min(start + MT_CHUNK, tl.size[t]);
+  return true;
+}
+
+// ---------------------------------------------------------------------------
+// SGD with momentum + weight decay on one element, w the fp32 weight:
+//   plain   d = g + wd*w                 (exact torch.optim.SGD math)
+//   SCALED  d = rt * (c*g + wd*w)        (c, rt from sgd_coeffs_kernel)
+//   m <- mu*m + d  (when has_momentum) ; returns w - lr*d
+// There is exactly one of these, inlined into the vector and the scalar loop
+// of the fp32 kernel and into the O2 kernel: every bit of w and m must agree
+// between the vector and the scalar path, and between a step with shadows and
+// one without. The FMAs are written out because contraction left to the
+// compiler differs between call sites: it turns c*g + wd*w into
+// fma(c, g, wd*w) in the vector loop but, in a scalar loop where it first
+// packs c*g and wd*w into one v_pk_mul_f32, into an unfused add. m is not
+// read or written when has_momentum is false.
+// ---------------------------------------------------------------------------
+template <bool SCALED>
+__device__ __forceinline__ float sgd_update(float w, float g, float& m,
+                                            bool has_momentum, float lr,
+                                            float mu, float wd, float c,
+                                            float rt) {
+  float d = SCALED ? rt * fmaf(c, g, wd * w) : fmaf(wd, w, g);
+  if (has_momentum) {
+    d = fmaf(mu, m, d);
+    m = d;
+  }
+  return fmaf(-lr, d, w);
+}
 
 // w16[t], where not null, is a 16-bit shadow of p[t] in the same memory order
 // (the conv layers' autocast copy of an fp32 weight): the kernel that produces
@@ -865,11 +914,6 @@ constexpr int MT_CHUNK = 1 << 13;
 // one step may refresh both kinds. The rounding is the float -> 16-bit
 // conversion's round-to-nearest-even, as in ATen's copy kernel. The flag only
 // selects the shadow store; the update arithmetic does not see it.
-//
-// A tensor whose pointers are all 16-byte aligned (8 for w16) moves as
-// float4s; any other, and the last size % 4 elements, go element by element.
-// The update expression is the same text in both loops so that both contract
-// into the same three FMAs and every bit of p and m agrees between them.
 struct MTTensorList {
   float* p[MT_MAX_TENSORS];
   float* g[MT_MAX_TENSORS];
@@ -883,19 +927,19 @@ struct MTTensorList {
 typedef __attribute__((ext_vector_type(4))) __bf16 mtbf16x4;
 typedef __attribute__((ext_vector_type(4))) _Float16 mthalfx4;
 
+// fp32 params. SCALED reads the clip coefficient gscale[0] and the per-tensor
+// ratio[t] from device memory; g is not modified. A tensor whose pointers are
+// all 16-byte aligned (8 for w16) moves as float4s; any other, and the last
+// size % 4 elements, go element by element.
+template <bool SCALED>
 __global__ void multi_tensor_sgd_kernel(MTTensorList tl, float lr, float mu,
-                                        float wd, bool has_momentum) {
-  int b = blockIdx.x;
-  int t = 0;
-  int chunk = 0;
-  for (; t < tl.ntensors; ++t) {
-    const int nchunks = (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
-    if (b < nchunks) { chunk = b; break; }
-    b -= nchunks;
-  }
-  if (t >= tl.ntensors) return;
-  const int start = chunk * MT_CHUNK;
-  const int end = min(start + MT_CHUNK, tl.size[t]);
+                                        float wd, bool has_momentum,
+                                        const float* __restrict__ gscale,
+                                        const float* __restrict__ ratio) {
+  int t, start, end;
+  if (!mt_locate(tl, t, start, end)) return;
+  const float c = SCALED ? gscale[0] : 1.f;
+  const float rt = SCALED ? ratio[t] : 1.f;
   float* p = tl.p[t];
   float* g = tl.g[t];
   float* m = has_momentum ? tl.m[t] : nullptr;
@@ -913,14 +957,9 @@ __global__ void multi_tensor_sgd_kernel(MTTensorList tl, float lr, float mu,
       *(float4*)gv = *(const float4*)(g + i);
       if (has_momentum) *(float4*)mv = *(const float4*)(m + i);
       #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float grad = gv[e] + wd * pv[e];
-        if (has_momentum) {
-          grad = mu * mv[e] + grad;
-          mv[e] = grad;
-        }
-        pv[e] -= lr * grad;
-      }
+      for (int e = 0; e < 4; ++e)
+        pv[e] = sgd_update<SCALED>(pv[e], gv[e], mv[e], has_momentum, lr, mu,
+                                   wd, c, rt);
       if (has_momentum) *(float4*)(m + i) = *(float4*)mv;
       *(float4*)(p + i) = *(float4*)pv;
       if (w16 != nullptr) {
@@ -939,12 +978,11 @@ __global__ void multi_tensor_sgd_kernel(MTTensorList tl, float lr, float mu,
     }
   }
   for (int i = tail + threadIdx.x; i < end; i += blockDim.x) {
-    float grad = g[i] + wd * p[i];
-    if (has_momentum) {
-      grad = mu * m[i] + grad;
-      m[i] = grad;
-    }
-    const float pn = p[i] - lr * grad;
+    float mv = 0.f;
+    if (has_momentum) mv = m[i];
+    const float pn = sgd_update<SCALED>(p[i], g[i], mv, has_momentum, lr, mu,
+                                        wd, c, rt);
+    if (has_momentum) m[i] = mv;
     p[i] = pn;
     if (w16 != nullptr) {
       if (half) ((_Float16*)w16)[i] = (_Float16)pn;
@@ -955,9 +993,8 @@ __global__ void multi_tensor_sgd_kernel(MTTensorList tl, float lr, float mu,
 
 // ---------------------------------------------------------------------------
 // Mixed-precision multi-tensor SGD (apex O2 equivalent): bf16 model
-// weights + bf16 grads + fp32 MASTER weights and momentum. The update runs
+// weights + bf16 grads + fp32 MASTER weights and momentum. sgd_update runs
 // in fp32 against the master; the bf16 parameter is the rounded copy.
-//   m <- mu*m + g + wd*master ; master <- master - lr*m ; p <- (bf16)master
 // ---------------------------------------------------------------------------
 struct MTMixedList {
   __bf16* p[MT_MAX_TENSORS];
@@ -968,30 +1005,25 @@ struct MTMixedList {
   int ntensors;
 };
 
+template <bool SCALED>
 __global__ void multi_tensor_sgd_o2_kernel(MTMixedList tl, float lr, float mu,
-                                           float wd, bool has_momentum) {
-  int b = blockIdx.x;
-  int t = 0;
-  int chunk = 0;
-  for (; t < tl.ntensors; ++t) {
-    const int nchunks = (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
-    if (b < nchunks) { chunk = b; break; }
-    b -= nchunks;
-  }
-  if (t >= tl.ntensors) return;
-  const int start = chunk * MT_CHUNK;
-  const int end = min(start + MT_CHUNK, tl.size[t]);
+                                           float wd, bool has_momentum,
+                                           const float* __restrict__ gscale,
+                                           const float* __restrict__ ratio) {
+  int t, start, end;
+  if (!mt_locate(tl, t, start, end)) return;
+  const float c = SCALED ? gscale[0] : 1.f;
+  const float rt = SCALED ? ratio[t] : 1.f;
   __bf16* p = tl.p[t];
   const __bf16* g = tl.g[t];
   float* w = tl.w[t];
   float* m = has_momentum ? tl.m[t] : nullptr;
   for (int i = start + threadIdx.x; i < end; i += blockDim.x) {
-    float grad = (float)g[i] + wd * w[i];
-    if (has_momentum) {
-      grad = mu * m[i] + grad;
-      m[i] = grad;
-    }
-    const float nw = w[i] - lr * grad;
+    float mv = 0.f;
+    if (has_momentum) mv = m[i];
+    const float nw = sgd_update<SCALED>(w[i], (float)g[i], mv, has_momentum,
+                                        lr, mu, wd, c, rt);
+    if (has_momentum) m[i] = mv;
     w[i] = nw;
     p[i] = (__bf16)nw;
   }
@@ -1025,17 +1057,8 @@ __global__ void multi_tensor_sqnorm_kernel(MTNormList tl,
   // 16 bytes of gradient per load: 4 floats or 8 bf16
   constexpr int VEC = 16 / sizeof(grad_t);
   typedef __attribute__((ext_vector_type(VEC))) grad_t gvec_t;
-  int b = blockIdx.x;
-  int t = 0;
-  int chunk = 0;
-  for (; t < tl.ntensors; ++t) {
-    const int nchunks = (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
-    if (b < nchunks) { chunk = b; break; }
-    b -= nchunks;
-  }
-  if (t >= tl.ntensors) return;
-  const int start = chunk * MT_CHUNK;
-  const int end = min(start + MT_CHUNK, tl.size[t]);
+  int t, start, end;
+  if (!mt_locate(tl, t, start, end)) return;
   const float* w = tl.w[t];
   const grad_t* g = (const grad_t*)tl.g[t];
   float sw = 0.f, sg = 0.f;
@@ -1083,8 +1106,8 @@ __global__ void multi_tensor_sqnorm_fold_kernel(MTNormList tl,
   const int t = blockIdx.x;
   if (t >= tl.ntensors) return;
   int off = chunk_base;
-  for (int u = 0; u < t; ++u) off += (tl.size[u] + MT_CHUNK - 1) / MT_CHUNK;
-  const int nchunks = (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
+  for (int u = 0; u < t; ++u) off += mt_chunks(tl.size[u]);
+  const int nchunks = mt_chunks(tl.size[t]);
   float sw = 0.f, sg = 0.f;
   for (int j = threadIdx.x; j < nchunks; j += blockDim.x) {
     sw += partials[off + j];
@@ -1144,124 +1167,6 @@ __global__ void sgd_coeffs_kernel(const float* __restrict__ sq,
 }
 
 // ---------------------------------------------------------------------------
-// multi_tensor_sgd_kernel with the gradient clipped and the update scaled per
-// tensor, both by coefficients read from device memory (sgd_coeffs_kernel):
-//   d = ratio[t] * (c*g + wd*p) ; m <- mu*m + d ; p <- p - lr*m
-// g is not modified. Shadows, vector/scalar split and the one-expression rule
-// are those of multi_tensor_sgd_kernel.
-// ---------------------------------------------------------------------------
-__global__ void multi_tensor_sgd_scaled_kernel(MTTensorList tl, float lr,
-                                               float mu, float wd,
-                                               bool has_momentum,
-                                               const float* __restrict__ gscale,
-                                               const float* __restrict__ ratio) {
-  int b = blockIdx.x;
-  int t = 0;
-  int chunk = 0;
-  for (; t < tl.ntensors; ++t) {
-    const int nchunks = (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
-    if (b < nchunks) { chunk = b; break; }
-    b -= nchunks;
-  }
-  if (t >= tl.ntensors) return;
-  const int start = chunk * MT_CHUNK;
-  const int end = min(start + MT_CHUNK, tl.size[t]);
-  const float c = gscale[0];
-  const float rt = ratio[t];
-  float* p = tl.p[t];
-  float* g = tl.g[t];
-  float* m = has_momentum ? tl.m[t] : nullptr;
-  void* w16 = tl.w16[t];
-  const bool half = tl.w16_half[t];
-  const bool vec = (((size_t)p | (size_t)g | (size_t)m) & 15) == 0 &&
-                   ((size_t)w16 & 7) == 0;
-  int tail = start;   // first element of the scalar loop
-  if (vec) {
-    tail = start + ((end - start) & ~3);
-    for (int i = start + 4 * threadIdx.x; i < tail; i += 4 * blockDim.x) {
-      float pv[4], gv[4], mv[4];
-      *(float4*)pv = *(const float4*)(p + i);
-      *(float4*)gv = *(const float4*)(g + i);
-      if (has_momentum) *(float4*)mv = *(const float4*)(m + i);
-      #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float grad = rt * (c * gv[e] + wd * pv[e]);
-        if (has_momentum) {
-          grad = mu * mv[e] + grad;
-          mv[e] = grad;
-        }
-        pv[e] -= lr * grad;
-      }
-      if (has_momentum) *(float4*)(m + i) = *(float4*)mv;
-      *(float4*)(p + i) = *(float4*)pv;
-      if (w16 != nullptr) {
-        if (half) {
-          mthalfx4 o;
-          #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (_Float16)pv[e];
-          *(mthalfx4*)((_Float16*)w16 + i) = o;
-        } else {
-          mtbf16x4 o;
-          #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (__bf16)pv[e];
-          *(mtbf16x4*)((__bf16*)w16 + i) = o;
-        }
-      }
-    }
-  }
-  for (int i = tail + threadIdx.x; i < end; i += blockDim.x) {
-    float grad = rt * (c * g[i] + wd * p[i]);
-    if (has_momentum) {
-      grad = mu * m[i] + grad;
-      m[i] = grad;
-    }
-    const float pn = p[i] - lr * grad;
-    p[i] = pn;
-    if (w16 != nullptr) {
-      if (half) ((_Float16*)w16)[i] = (_Float16)pn;
-      else ((__bf16*)w16)[i] = (__bf16)pn;
-    }
-  }
-}
-
-// multi_tensor_sgd_o2_kernel with the same two coefficients:
-//   d = ratio[t] * (c*g + wd*master) ; m <- mu*m + d ;
-//   master <- master - lr*m ; p <- (bf16)master
-__global__ void multi_tensor_sgd_o2_scaled_kernel(MTMixedList tl, float lr,
-                                                  float mu, float wd,
-                                                  bool has_momentum,
-                                                  const float* __restrict__ gscale,
-                                                  const float* __restrict__ ratio) {
-  int b = blockIdx.x;
-  int t = 0;
-  int chunk = 0;
-  for (; t < tl.ntensors; ++t) {
-    const int nchunks = (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
-    if (b < nchunks) { chunk = b; break; }
-    b -= nchunks;
-  }
-  if (t >= tl.ntensors) return;
-  const int start = chunk * MT_CHUNK;
-  const int end = min(start + MT_CHUNK, tl.size[t]);
-  const float c = gscale[0];
-  const float rt = ratio[t];
-  __bf16* p = tl.p[t];
-  const __bf16* g = tl.g[t];
-  float* w = tl.w[t];
-  float* m = has_momentum ? tl.m[t] : nullptr;
-  for (int i = start + threadIdx.x; i < end; i += blockDim.x) {
-    float grad = rt * (c * (float)g[i] + wd * w[i]);
-    if (has_momentum) {
-      grad = mu * m[i] + grad;
-      m[i] = grad;
-    }
-    const float nw = w[i] - lr * grad;
-    w[i] = nw;
-    p[i] = (__bf16)nw;
-  }
-}
-
-// ---------------------------------------------------------------------------
 // Multi-tensor unscale + inf/nan check (fp16 loss-scaler backward pass).
 // ---------------------------------------------------------------------------
 struct MTGradList {
@@ -1272,17 +1177,8 @@ struct MTGradList {
 
 __global__ void multi_tensor_unscale_kernel(MTGradList tl, float inv_scale,
                                             int* __restrict__ found_inf) {
-  int b = blockIdx.x;
-  int t = 0;
-  int chunk = 0;
-  for (; t < tl.ntensors; ++t) {
-    const int nchunks = (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
-    if (b < nchunks) { chunk = b; break; }
-    b -= nchunks;
-  }
-  if (t >= tl.ntensors) return;
-  const int start = chunk * MT_CHUNK;
-  const int end = min(start + MT_CHUNK, tl.size[t]);
+  int t, start, end;
+  if (!mt_locate(tl, t, start, end)) return;
   float* g = tl.g[t];
   bool bad = false;
   for (int i = start + threadIdx.x; i < end; i += blockDim.x) {
@@ -2232,6 +2128,24 @@ at::Tensor xent_mix_bwd(at::Tensor logits, at::Tensor target_a,
   return dx;
 }
 
+// One launch of a multi-tensor kernel in the making. The batching rule lives
+// here and in mt_chunks only: at most MT_MAX_TENSORS tensors per launch,
+// mt_chunks(numel) blocks per tensor.
+template <typename List>
+struct MTBatch {
+  List tl;
+  int nblocks = 0;
+  MTBatch() { tl.ntensors = 0; }
+  bool full() const { return tl.ntensors == MT_MAX_TENSORS; }
+  // Takes a tensor of numel elements; returns its slot in tl.
+  int push(int64_t numel) {
+    const int t = tl.ntensors++;
+    tl.size[t] = (int)numel;
+    nblocks += mt_chunks(tl.size[t]);
+    return t;
+  }
+};
+
 // gscale/ratio null: the plain kernel. Otherwise the scaled one, with
 // ratio[i] the coefficient of params[i].
 static void multi_tensor_sgd_impl(std::vector<at::Tensor>& params,
@@ -2242,24 +2156,25 @@ static void multi_tensor_sgd_impl(std::vector<at::Tensor>& params,
                                   std::vector<c10::optional<at::Tensor>>& w16s,
                                   const float* gscale, const float* ratio) {
   const bool has_momentum = !bufs.empty();
+  const bool scaled = gscale != nullptr;
   TORCH_CHECK(params.size() == grads.size());
   TORCH_CHECK(!has_momentum || bufs.size() == params.size(),
               "multi_tensor_sgd: one momentum buffer per param");
   TORCH_CHECK(w16s.empty() || w16s.size() == params.size(),
               "multi_tensor_sgd: one w16 entry (or None) per param");
   auto stream = cur_stream();
-  size_t i = 0;
-  while (i < params.size()) {
-    MTTensorList tl;
-    int nblocks = 0;
-    int t = 0;
-    for (; t < MT_MAX_TENSORS && i < params.size(); ++t, ++i) {
+  for (size_t i = 0; i < params.size();) {
+    MTBatch<MTTensorList> b;
+    MTTensorList& tl = b.tl;
+    const size_t first = i;
+    for (; !b.full() && i < params.size(); ++i) {
       auto& p = params[i];
       TORCH_CHECK(p.is_cuda() && p.is_non_overlapping_and_dense() &&
                   p.scalar_type() == at::kFloat,
                   "multi_tensor_sgd expects dense fp32 params");
       TORCH_CHECK(grads[i].strides() == p.strides(),
                   "multi_tensor_sgd: grad/param layout mismatch");
+      const int t = b.push(p.numel());
       tl.p[t] = p.data_ptr<float>();
       tl.g[t] = grads[i].data_ptr<float>();
       tl.m[t] = has_momentum ? bufs[i].data_ptr<float>() : nullptr;
@@ -2276,20 +2191,12 @@ static void multi_tensor_sgd_impl(std::vector<at::Tensor>& params,
         tl.w16[t] = w16.data_ptr();
         tl.w16_half[t] = w16.scalar_type() == at::kHalf;
       }
-      tl.size[t] = (int)p.numel();
-      nblocks += (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
     }
-    tl.ntensors = t;
-    if (gscale == nullptr) {
-      hipLaunchKernelGGL(multi_tensor_sgd_kernel, dim3(nblocks), dim3(256), 0,
-                         stream, tl, (float)lr, (float)momentum,
-                         (float)weight_decay, has_momentum);
-    } else {
-      hipLaunchKernelGGL(multi_tensor_sgd_scaled_kernel, dim3(nblocks),
-                         dim3(256), 0, stream, tl, (float)lr, (float)momentum,
-                         (float)weight_decay, has_momentum, gscale,
-                         ratio + (i - t));
-    }
+    hipLaunchKernelGGL(scaled ? multi_tensor_sgd_kernel<true>
+                              : multi_tensor_sgd_kernel<false>,
+                       dim3(b.nblocks), dim3(256), 0, stream, tl, (float)lr,
+                       (float)momentum, (float)weight_decay, has_momentum,
+                       gscale, scaled ? ratio + first : nullptr);
   }
 }
 
@@ -2334,17 +2241,17 @@ static void multi_tensor_sgd_o2_impl(std::vector<at::Tensor>& params,
                                      double weight_decay,
                                      const float* gscale, const float* ratio) {
   const bool has_momentum = !bufs.empty();
+  const bool scaled = gscale != nullptr;
   TORCH_CHECK(params.size() == grads.size() &&
               params.size() == masters.size());
   TORCH_CHECK(!has_momentum || bufs.size() == params.size(),
               "multi_tensor_sgd_o2: one momentum buffer per param");
   auto stream = cur_stream();
-  size_t i = 0;
-  while (i < params.size()) {
-    MTMixedList tl;
-    int nblocks = 0;
-    int t = 0;
-    for (; t < MT_MAX_TENSORS && i < params.size(); ++t, ++i) {
+  for (size_t i = 0; i < params.size();) {
+    MTBatch<MTMixedList> b;
+    MTMixedList& tl = b.tl;
+    const size_t first = i;
+    for (; !b.full() && i < params.size(); ++i) {
       auto& p = params[i];
       TORCH_CHECK(p.is_cuda() && p.is_non_overlapping_and_dense() &&
                   p.scalar_type() == at::ScalarType::BFloat16,
@@ -2355,24 +2262,17 @@ static void multi_tensor_sgd_o2_impl(std::vector<at::Tensor>& params,
       TORCH_CHECK(masters[i].strides() == p.strides() &&
                   masters[i].scalar_type() == at::kFloat,
                   "multi_tensor_sgd_o2: master layout/dtype mismatch");
+      const int t = b.push(p.numel());
       tl.p[t] = reinterpret_cast<__bf16*>(p.data_ptr());
       tl.g[t] = reinterpret_cast<const __bf16*>(grads[i].data_ptr());
       tl.w[t] = masters[i].data_ptr<float>();
       tl.m[t] = has_momentum ? bufs[i].data_ptr<float>() : nullptr;
-      tl.size[t] = (int)p.numel();
-      nblocks += (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
     }
-    tl.ntensors = t;
-    if (gscale == nullptr) {
-      hipLaunchKernelGGL(multi_tensor_sgd_o2_kernel, dim3(nblocks), dim3(256),
-                         0, stream, tl, (float)lr, (float)momentum,
-                         (float)weight_decay, has_momentum);
-    } else {
-      hipLaunchKernelGGL(multi_tensor_sgd_o2_scaled_kernel, dim3(nblocks),
-                         dim3(256), 0, stream, tl, (float)lr, (float)momentum,
-                         (float)weight_decay, has_momentum, gscale,
-                         ratio + (i - t));
-    }
+    hipLaunchKernelGGL(scaled ? multi_tensor_sgd_o2_kernel<true>
+                              : multi_tensor_sgd_o2_kernel<false>,
+                       dim3(b.nblocks), dim3(256), 0, stream, tl, (float)lr,
+                       (float)momentum, (float)weight_decay, has_momentum,
+                       gscale, scaled ? ratio + first : nullptr);
   }
 }
 
@@ -2410,7 +2310,7 @@ void multi_tensor_sqnorm(std::vector<at::Tensor> ws,
   if (ws.empty()) return;
   const int n = (int)ws.size();
   long total_chunks = 0;
-  for (auto& w : ws) total_chunks += (w.numel() + MT_CHUNK - 1) / MT_CHUNK;
+  for (auto& w : ws) total_chunks += mt_chunks(w.numel());
   auto dev_f32 = [&](const at::Tensor& x) {
     return x.is_cuda() && x.scalar_type() == at::kFloat &&
            x.is_contiguous() && x.device() == ws[0].device();
@@ -2425,15 +2325,13 @@ void multi_tensor_sqnorm(std::vector<at::Tensor> ws,
   const int pstride = (int)partials.size(1);
   auto stream = cur_stream();
   int chunk_base = 0;
-  size_t i = 0;
-  while (i < ws.size()) {
-    MTNormList tl;
+  for (size_t i = 0; i < ws.size();) {
+    MTBatch<MTNormList> b;
+    MTNormList& tl = b.tl;
     const auto gdtype = gs[i].scalar_type();
     const int tensor_base = (int)i;
-    int nblocks = 0;
-    int t = 0;
-    for (; t < MT_MAX_TENSORS && i < ws.size() &&
-           gs[i].scalar_type() == gdtype; ++t, ++i) {
+    for (; !b.full() && i < ws.size() && gs[i].scalar_type() == gdtype;
+         ++i) {
       auto& w = ws[i];
       auto& g = gs[i];
       TORCH_CHECK(w.is_cuda() && w.is_non_overlapping_and_dense() &&
@@ -2445,28 +2343,22 @@ void multi_tensor_sqnorm(std::vector<at::Tensor> ws,
                   (gdtype == at::kFloat || gdtype == at::kBFloat16),
                   "multi_tensor_sqnorm expects dense fp32 or bf16 grads of "
                   "the weights' sizes");
+      const int t = b.push(w.numel());
       tl.w[t] = w.data_ptr<float>();
       tl.g[t] = g.data_ptr();
-      tl.size[t] = (int)w.numel();
-      nblocks += (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
     }
-    tl.ntensors = t;
-    if (nblocks > 0) {
-      if (gdtype == at::kFloat) {
-        hipLaunchKernelGGL(multi_tensor_sqnorm_kernel<float>, dim3(nblocks),
-                           dim3(256), 0, stream, tl,
-                           partials.data_ptr<float>(), chunk_base, pstride);
-      } else {
-        hipLaunchKernelGGL(multi_tensor_sqnorm_kernel<__bf16>, dim3(nblocks),
-                           dim3(256), 0, stream, tl,
-                           partials.data_ptr<float>(), chunk_base, pstride);
-      }
+    if (b.nblocks > 0) {
+      hipLaunchKernelGGL(gdtype == at::kFloat
+                             ? multi_tensor_sqnorm_kernel<float>
+                             : multi_tensor_sqnorm_kernel<__bf16>,
+                         dim3(b.nblocks), dim3(256), 0, stream, tl,
+                         partials.data_ptr<float>(), chunk_base, pstride);
     }
-    hipLaunchKernelGGL(multi_tensor_sqnorm_fold_kernel, dim3(t), dim3(256), 0,
-                       stream, tl, partials.data_ptr<float>(),
+    hipLaunchKernelGGL(multi_tensor_sqnorm_fold_kernel, dim3(tl.ntensors),
+                       dim3(256), 0, stream, tl, partials.data_ptr<float>(),
                        sq.data_ptr<float>(), chunk_base, pstride, tensor_base,
                        n);
-    chunk_base += nblocks;
+    chunk_base += b.nblocks;
   }
 }
 
@@ -2500,22 +2392,16 @@ at::Tensor multi_tensor_unscale(std::vector<at::Tensor> grads, double inv_scale)
   TORCH_CHECK(!grads.empty());
   auto found = at::zeros({1}, grads[0].options().dtype(at::kInt));
   auto stream = cur_stream();
-  size_t i = 0;
-  while (i < grads.size()) {
-    MTGradList tl;
-    int nblocks = 0;
-    int t = 0;
-    for (; t < MT_MAX_TENSORS && i < grads.size(); ++t, ++i) {
+  for (size_t i = 0; i < grads.size();) {
+    MTBatch<MTGradList> b;
+    for (; !b.full() && i < grads.size(); ++i) {
       TORCH_CHECK(grads[i].is_cuda() && grads[i].is_non_overlapping_and_dense() &&
                   grads[i].scalar_type() == at::kFloat,
                   "multi_tensor_unscale expects dense fp32 grads");
-      tl.g[t] = grads[i].data_ptr<float>();
-      tl.size[t] = (int)grads[i].numel();
-      nblocks += (tl.size[t] + MT_CHUNK - 1) / MT_CHUNK;
+      b.tl.g[b.push(grads[i].numel())] = grads[i].data_ptr<float>();
     }
-    tl.ntensors = t;
-    hipLaunchKernelGGL(multi_tensor_unscale_kernel, dim3(nblocks), dim3(256),
-                       0, stream, tl, (float)inv_scale,
+    hipLaunchKernelGGL(multi_tensor_unscale_kernel, dim3(b.nblocks), dim3(256),
+                       0, stream, b.tl, (float)inv_scale,
                        found.data_ptr<int>());
   }
   return found;
@@ -2758,6 +2644,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("weight_decay"), py::arg("gscale"), py::arg("ratio"));
   m.def("multi_tensor_unscale", &multi_tensor_unscale,
         "multi-tensor grad unscale + inf/nan check");
+  // ops/sgd.py keeps its own values for the CPU fallback; a test compares them
+  m.attr("MT_CHUNK") = MT_CHUNK;
+  m.attr("MT_MAX_TENSORS") = MT_MAX_TENSORS;
+  m.attr("LARS_EPS") = LARS_EPS;
+  m.attr("CLIP_EPS") = CLIP_EPS;
   m.def("gap_fwd", &gap_fwd, "global average pool forward (NCHW/NHWC)");
   m.def("gap_bwd", &gap_bwd, "global average pool backward");
   m.def("maxpool_fwd", &maxpool_fwd,

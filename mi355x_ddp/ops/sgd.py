@@ -53,16 +53,18 @@ measured in this project.
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 
 from . import _backend
 from .conv import WeightShadow, shadow_of, weight_shadows_wanted
 
-LARS_EPS = 1e-8   # in the trust ratio's denominator (csrc: LARS_EPS)
-CLIP_EPS = 1e-6   # torch.nn.utils.clip_grad_norm_'s (csrc: CLIP_EPS)
-_MT_CHUNK = 1 << 13   # csrc: MT_CHUNK, elements per block
+# The extension exports its values under the same names (_C.MT_CHUNK for the
+# last); these serve the CPU fallback, which runs with no extension built.
+LARS_EPS = 1e-8   # in the trust ratio's denominator
+CLIP_EPS = 1e-6   # torch.nn.utils.clip_grad_norm_'s
+_MT_CHUNK = 1 << 13   # elements per block
 
 
 class _NormBuffers:
@@ -112,12 +114,13 @@ class FusedSGD(torch.optim.Optimizer):
             return None
         return getattr(self, "_grad_norm", None)
 
-    def _gather(self, group):
+    def _gather(self, group) -> "_Gathered":
         """The group's tensors that have a gradient, split into the fp32 and
         the bf16 (O2) path; creates masters and momentum buffers."""
+        # plain local lists: this loop is host time of every step
         p32, g32, m32, s32 = [], [], [], []
         p16, g16, w16, m16 = [], [], [], []
-        momentum = group["momentum"]
+        has_momentum = group["momentum"] != 0
         for p in group["params"]:
             if p.grad is None:
                 continue
@@ -125,23 +128,22 @@ class FusedSGD(torch.optim.Optimizer):
             if p.dtype == torch.bfloat16:
                 if "master" not in state:
                     state["master"] = p.detach().float()
-                if momentum != 0 and "momentum_buffer" not in state:
-                    state["momentum_buffer"] = torch.zeros_like(
-                        state["master"])
+                w, ms = state["master"], m16
                 p16.append(p)
                 g16.append(p.grad)
-                w16.append(state["master"])
-                if momentum != 0:
-                    m16.append(state["momentum_buffer"])
+                w16.append(w)
             else:
-                if momentum != 0 and "momentum_buffer" not in state:
-                    state["momentum_buffer"] = torch.zeros_like(p)
+                w, ms = p, m32
                 p32.append(p)
                 g32.append(p.grad)
                 s32.append(shadow_of(p))
-                if momentum != 0:
-                    m32.append(state["momentum_buffer"])
-        return p32, g32, m32, s32, p16, g16, w16, m16
+            if has_momentum:
+                if "momentum_buffer" not in state:
+                    state["momentum_buffer"] = torch.zeros_like(w)
+                ms.append(state["momentum_buffer"])
+        if not has_momentum:
+            m32 = m16 = None
+        return _Gathered(p32, g32, m32, s32, p16, g16, w16, m16)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -151,20 +153,9 @@ class FusedSGD(torch.optim.Optimizer):
                 loss = closure()
         if any(_group_scaled(g) for g in self.param_groups):
             self._step_scaled()
-            return loss
-        for group in self.param_groups:
-            p32, g32, m32, s32, p16, g16, w16, m16 = self._gather(group)
-            momentum = group["momentum"]
-            if p32:
-                fused_sgd_step(p32, g32, m32 if momentum != 0 else None,
-                               lr=group["lr"], momentum=momentum,
-                               weight_decay=group["weight_decay"],
-                               shadows=s32)
-            if p16:
-                fused_sgd_o2_step(p16, g16, w16,
-                                  m16 if momentum != 0 else None,
-                                  lr=group["lr"], momentum=momentum,
-                                  weight_decay=group["weight_decay"])
+        else:
+            for group in self.param_groups:
+                _step_group(group, self._gather(group))
         return loss
 
     def _step_scaled(self) -> None:
@@ -173,12 +164,12 @@ class FusedSGD(torch.optim.Optimizer):
         # the order of the norm's tensor list: group by group, a group's fp32
         # tensors before its bf16 ones, so each path's ratios are one slice
         ws, gs, excluded, ranges = [], [], [], []
-        for p32, g32, _, _, p16, g16, w16, _ in gathered:
+        for got in gathered:
             lo = len(ws)
-            ws += p32 + w16
-            gs += g32 + g16
-            excluded += [p.ndim <= 1 for p in p32 + p16]
-            ranges.append((lo, lo + len(p32), len(ws)))
+            ws += got.p32 + got.w16
+            gs += got.g32 + got.g16
+            excluded += [p.ndim <= 1 for p in got.p32 + got.p16]
+            ranges.append((lo, lo + len(got.p32), len(ws)))
         if not ws:
             return
         native = _backend.native_enabled(ws[0])
@@ -199,8 +190,6 @@ class FusedSGD(torch.optim.Optimizer):
                 zip(self.param_groups, gathered, ranges)):
             if lo == hi:
                 continue
-            p32, g32, m32, s32, p16, g16, w16, m16 = got
-            momentum = group["momentum"]
             wd = group["weight_decay"]
             max_norm = group.get("clip_grad_norm", 0.0)
             lars = bool(group.get("lars", False))
@@ -214,17 +203,36 @@ class FusedSGD(torch.optim.Optimizer):
             else:
                 gscale, ratio, self._grad_norm = sgd_coeffs_torch(
                     sq_w, sq_g, excluded, max_norm, lars, eta, wd)
-            if p32:
-                fused_sgd_step(p32, g32, m32 if momentum != 0 else None,
-                               lr=group["lr"], momentum=momentum,
-                               weight_decay=wd, shadows=s32,
-                               gscale=gscale, ratio=ratio[lo:mid])
-            if p16:
-                fused_sgd_o2_step(p16, g16, w16,
-                                  m16 if momentum != 0 else None,
-                                  lr=group["lr"], momentum=momentum,
-                                  weight_decay=wd,
-                                  gscale=gscale, ratio=ratio[mid:hi])
+            _step_group(group, got, gscale, ratio[lo:mid], ratio[mid:hi])
+
+
+class _Gathered(NamedTuple):
+    """One group's tensors that have a gradient, by path. The momentum lists
+    are None when the group has no momentum."""
+    # fp32 path: params, grads, momentum buffers, weight shadows (None where
+    # a param has none)
+    p32: list
+    g32: list
+    m32: Optional[list]
+    s32: list
+    # O2 path: bf16 params, bf16 grads, fp32 masters, fp32 momentum buffers
+    p16: list
+    g16: list
+    w16: list
+    m16: Optional[list]
+
+
+def _step_group(group, got: _Gathered, gscale=None, ratio32=None,
+                ratio16=None) -> None:
+    """Steps one group; without `gscale` and the ratios, the plain step."""
+    lr, momentum = group["lr"], group["momentum"]
+    wd = group["weight_decay"]
+    if got.p32:
+        fused_sgd_step(got.p32, got.g32, got.m32, lr, momentum, wd, got.s32,
+                       gscale, ratio32)
+    if got.p16:
+        fused_sgd_o2_step(got.p16, got.g16, got.w16, got.m16, lr, momentum,
+                          wd, gscale, ratio16)
 
 
 def sgd_coeffs_torch(sq_w: torch.Tensor, sq_g: torch.Tensor,
@@ -250,6 +258,27 @@ def sgd_coeffs_torch(sq_w: torch.Tensor, sq_g: torch.Tensor,
     return c.reshape(1), ratio, norm
 
 
+def _update_torch(ws, grads, momentum_bufs, lr, momentum, weight_decay,
+                  gscale, ratio, params16=None) -> None:
+    """The update in torch, same math (used on CPU and for parity tests), on
+    the fp32 weights `ws`. With `params16` (the O2 path) `ws` are the masters
+    of bf16 parameters, which get the rounded copy."""
+    for i, (w, g) in enumerate(zip(ws, grads)):
+        if params16 is not None:
+            g = g.float()
+        if gscale is not None:
+            g = ratio[i] * (gscale[0] * g + weight_decay * w)
+        elif weight_decay != 0:
+            g = g.add(w, alpha=weight_decay)
+        if momentum_bufs is not None:
+            buf = momentum_bufs[i]
+            buf.mul_(momentum).add_(g)
+            g = buf
+        w.add_(g, alpha=-lr)
+        if params16 is not None:
+            params16[i].copy_(w)
+
+
 def fused_sgd_step(params: List[torch.Tensor], grads: List[torch.Tensor],
                    momentum_bufs: Optional[List[torch.Tensor]],
                    lr: float, momentum: float, weight_decay: float,
@@ -269,39 +298,30 @@ def fused_sgd_step(params: List[torch.Tensor], grads: List[torch.Tensor],
             live.append((p, sh))
         else:
             sh.invalidate()
-    if params and _backend.native_enabled(params[0]):
-        w16s = []
-        if live:
-            keep = {id(sh) for _, sh in live}
-            w16s = [sh.w16 if sh is not None and id(sh) in keep else None
-                    for sh in shadows]
-        bufs = momentum_bufs if momentum_bufs is not None else []
-        if gscale is None:
-            _backend.C().multi_tensor_sgd(params, grads, bufs,
-                                          lr, momentum, weight_decay, w16s)
-        else:
-            _backend.C().multi_tensor_sgd_scaled(params, grads, bufs,
-                                                 lr, momentum, weight_decay,
-                                                 gscale, ratio, w16s)
-        if live:
-            _backend.C().multi_tensor_build_wT([sh.w16 for _, sh in live],
-                                               [sh.wT for _, sh in live])
-            for p, sh in live:
-                sh.mark_fresh(p)
+    if not (params and _backend.native_enabled(params[0])):
+        for _, sh in live:
+            sh.invalidate()
+        _update_torch(params, grads, momentum_bufs, lr, momentum,
+                      weight_decay, gscale, ratio)
         return
-    for _, sh in live:
-        sh.invalidate()
-    # torch fallback, same math (used on CPU and for parity tests)
-    for i, (p, g) in enumerate(zip(params, grads)):
-        if gscale is not None:
-            g = ratio[i] * (gscale[0] * g + weight_decay * p)
-        elif weight_decay != 0:
-            g = g.add(p, alpha=weight_decay)
-        if momentum_bufs is not None:
-            buf = momentum_bufs[i]
-            buf.mul_(momentum).add_(g)
-            g = buf
-        p.add_(g, alpha=-lr)
+    w16s = []
+    if live:
+        keep = {id(sh) for _, sh in live}
+        w16s = [sh.w16 if sh is not None and id(sh) in keep else None
+                for sh in shadows]
+    bufs = momentum_bufs if momentum_bufs is not None else []
+    if gscale is None:
+        _backend.C().multi_tensor_sgd(params, grads, bufs,
+                                      lr, momentum, weight_decay, w16s)
+    else:
+        _backend.C().multi_tensor_sgd_scaled(params, grads, bufs,
+                                             lr, momentum, weight_decay,
+                                             gscale, ratio, w16s)
+    if live:
+        _backend.C().multi_tensor_build_wT([sh.w16 for _, sh in live],
+                                           [sh.wT for _, sh in live])
+        for p, sh in live:
+            sh.mark_fresh(p)
 
 
 def fused_sgd_o2_step(params: List[torch.Tensor], grads: List[torch.Tensor],
@@ -312,25 +332,15 @@ def fused_sgd_o2_step(params: List[torch.Tensor], grads: List[torch.Tensor],
                       ratio: Optional[torch.Tensor] = None) -> None:
     """bf16 params/grads, fp32 master + momentum (apex-O2 update); scaled as
     in fused_sgd_step when `gscale` and `ratio` are given."""
-    if params and _backend.native_enabled(params[0]):
-        bufs = momentum_bufs if momentum_bufs is not None else []
-        if gscale is None:
-            _backend.C().multi_tensor_sgd_o2(
-                params, grads, masters, bufs, lr, momentum, weight_decay)
-        else:
-            _backend.C().multi_tensor_sgd_o2_scaled(
-                params, grads, masters, bufs, lr, momentum, weight_decay,
-                gscale, ratio)
+    if not (params and _backend.native_enabled(params[0])):
+        _update_torch(masters, grads, momentum_bufs, lr, momentum,
+                      weight_decay, gscale, ratio, params16=params)
         return
-    for i, (p, g, w) in enumerate(zip(params, grads, masters)):
-        gf = g.float()
-        if gscale is not None:
-            gf = ratio[i] * (gscale[0] * gf + weight_decay * w)
-        elif weight_decay != 0:
-            gf = gf.add(w, alpha=weight_decay)
-        if momentum_bufs is not None:
-            buf = momentum_bufs[i]
-            buf.mul_(momentum).add_(gf)
-            gf = buf
-        w.add_(gf, alpha=-lr)
-        p.copy_(w)
+    bufs = momentum_bufs if momentum_bufs is not None else []
+    if gscale is None:
+        _backend.C().multi_tensor_sgd_o2(
+            params, grads, masters, bufs, lr, momentum, weight_decay)
+    else:
+        _backend.C().multi_tensor_sgd_o2_scaled(
+            params, grads, masters, bufs, lr, momentum, weight_decay,
+            gscale, ratio)

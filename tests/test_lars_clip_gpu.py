@@ -83,6 +83,18 @@ def _sq64(ts):
     return torch.stack([t.double().pow(2).sum() for t in ts])
 
 
+def test_constants_agree_with_extension():
+    """ops/sgd.py keeps its own values for the CPU fallback."""
+    from mi355x_ddp.ops import sgd
+    C = _backend.C()
+    assert C.MT_CHUNK == sgd._MT_CHUNK == CHUNK
+    # the kernels hold these as float, and torch rounds the Python values to
+    # float where it adds them to fp32 tensors: equal as float
+    for name in ("LARS_EPS", "CLIP_EPS"):
+        mine = torch.tensor(getattr(sgd, name), dtype=torch.float32).item()
+        assert getattr(C, name) == mine, name
+
+
 # ---- 1. sums of squares -------------------------------------------------------
 
 @pytest.mark.parametrize("gdtype", ["fp32", "bf16"])
@@ -261,7 +273,9 @@ def test_scaled_update_vector_and_scalar_paths_agree(mu):
             for _ in range(2)]
     assert ws[0].data_ptr() % 16 == 0 and ws[1].data_ptr() % 16 != 0
     ratio = torch.tensor([1.3, 1.3], device=DEV)
-    gscale = torch.tensor([0.5], device=DEV)
+    # no power of two: gscale*g rounds, so a path that fuses it into an FMA
+    # and one that does not give different bits
+    gscale = torch.tensor([0.3], device=DEV)
     _backend.C().multi_tensor_sgd_scaled(ws, gs, ms, LR, mu, WD, gscale,
                                          ratio, w16s)
     assert not torch.equal(ws[0], w)

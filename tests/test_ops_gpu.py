@@ -258,6 +258,23 @@ def test_multi_tensor_unscale_detects_inf_and_nan():
     found = _backend.C().multi_tensor_unscale([g1, g2], 1.0)
     assert found.item() == 1
 
+    # 40 tensors: two launches (32 per launch), sizes around the 8192-element
+    # chunk. Powers of two times a power of two: every product is exact.
+    sizes = [1, 3, 8191, 8192, 8193, 2 * 8192 + 5]
+    vals = [2.0 ** (i % 7 - 3) for i in range(40)]
+    gs = [torch.full((sizes[i % 6],), vals[i], device=DEV) for i in range(40)]
+    found = _backend.C().multi_tensor_unscale(gs, 0.25)
+    assert found.item() == 0
+    for g, v in zip(gs, vals):
+        assert torch.equal(g, torch.full_like(g, v * 0.25))
+    assert gs[35].numel() == 2 * 8192 + 5   # in the second launch
+    gs[35][-1] = float("inf")
+    assert _backend.C().multi_tensor_unscale(gs, 1.0).item() == 1
+    gs[35][-1] = 0.0
+    assert gs[4].numel() == 8193            # element 8192: its second chunk
+    gs[4][8192] = float("nan")
+    assert _backend.C().multi_tensor_unscale(gs, 1.0).item() == 1
+
 
 def test_fused_sgd_optimizer_gpu_matches_torch():
     from mi355x_ddp.ops import FusedSGD
