@@ -907,6 +907,16 @@ __device__ __forceinline__ float sgd_update(float w, float g, float& m,
   return fmaf(-lr, d, w);
 }
 
+// Exponential moving average of a weight on one element: e <- d*e + omd*w,
+// with omd = 1.f - d formed once on the host. Exact at both ends: d = 0 gives
+// w bit for bit (0*e + w), d = 1 leaves e. One definition for the vector and
+// the scalar loop of the fp32 SGD kernel, the O2 kernel and multi_tensor_ema;
+// the fmaf is written out for the reason given above sgd_update.
+__device__ __forceinline__ float ema_update(float e, float w, float d,
+                                            float omd) {
+  return fmaf(d, e, omd * w);
+}
+
 // w16[t], where not null, is a 16-bit shadow of p[t] in the same memory order
 // (the conv layers' autocast copy of an fp32 weight): the kernel that produces
 // the new weight also stores its rounded copy, so no cast kernel runs per
@@ -914,11 +924,15 @@ __device__ __forceinline__ float sgd_update(float w, float g, float& m,
 // one step may refresh both kinds. The rounding is the float -> 16-bit
 // conversion's round-to-nearest-even, as in ATen's copy kernel. The flag only
 // selects the shadow store; the update arithmetic does not see it.
+// ema[t], where not null, is the tensor's averaged weight (ema_update); only
+// the EMA instantiations read it. sizeof(MTTensorList) = 5*256 + 128 + 32 + 4
+// = 1444 -> 1448 bytes of the 4 KiB of kernel-argument space.
 struct MTTensorList {
   float* p[MT_MAX_TENSORS];
   float* g[MT_MAX_TENSORS];
   float* m[MT_MAX_TENSORS];
   void* w16[MT_MAX_TENSORS];
+  float* ema[MT_MAX_TENSORS];
   int size[MT_MAX_TENSORS];
   bool w16_half[MT_MAX_TENSORS];
   int ntensors;
@@ -930,12 +944,15 @@ typedef __attribute__((ext_vector_type(4))) _Float16 mthalfx4;
 // fp32 params. SCALED reads the clip coefficient gscale[0] and the per-tensor
 // ratio[t] from device memory; g is not modified. A tensor whose pointers are
 // all 16-byte aligned (8 for w16) moves as float4s; any other, and the last
-// size % 4 elements, go element by element.
-template <bool SCALED>
+// size % 4 elements, go element by element. EMA also averages the new weight
+// into ema[t] (decay d, omd = 1 - d) where that is not null; without EMA the
+// kernel does not touch tl.ema, d or omd.
+template <bool SCALED, bool EMA>
 __global__ void multi_tensor_sgd_kernel(MTTensorList tl, float lr, float mu,
                                         float wd, bool has_momentum,
                                         const float* __restrict__ gscale,
-                                        const float* __restrict__ ratio) {
+                                        const float* __restrict__ ratio,
+                                        float d, float omd) {
   int t, start, end;
   if (!mt_locate(tl, t, start, end)) return;
   const float c = SCALED ? gscale[0] : 1.f;
@@ -944,24 +961,34 @@ __global__ void multi_tensor_sgd_kernel(MTTensorList tl, float lr, float mu,
   float* g = tl.g[t];
   float* m = has_momentum ? tl.m[t] : nullptr;
   void* w16 = tl.w16[t];
+  float* ema = EMA ? tl.ema[t] : nullptr;
   const bool half = tl.w16_half[t];
-  const bool vec = (((size_t)p | (size_t)g | (size_t)m) & 15) == 0 &&
+  const bool vec = (((size_t)p | (size_t)g | (size_t)m | (size_t)ema) & 15)
+                       == 0 &&
                    ((size_t)w16 & 7) == 0;
   int tail = start;   // first element of the scalar loop
   if (vec) {
     // start is a multiple of MT_CHUNK, so every float4 below is aligned
     tail = start + ((end - start) & ~3);
     for (int i = start + 4 * threadIdx.x; i < tail; i += 4 * blockDim.x) {
-      float pv[4], gv[4], mv[4];
+      float pv[4], gv[4], mv[4], ev[4];
       *(float4*)pv = *(const float4*)(p + i);
       *(float4*)gv = *(const float4*)(g + i);
       if (has_momentum) *(float4*)mv = *(const float4*)(m + i);
+      // with the other loads: after the stores to m and p, which might alias
+      // it for all the compiler knows, this load could not move up here
+      if (EMA && ema != nullptr) *(float4*)ev = *(const float4*)(ema + i);
       #pragma unroll
       for (int e = 0; e < 4; ++e)
         pv[e] = sgd_update<SCALED>(pv[e], gv[e], mv[e], has_momentum, lr, mu,
                                    wd, c, rt);
       if (has_momentum) *(float4*)(m + i) = *(float4*)mv;
       *(float4*)(p + i) = *(float4*)pv;
+      if (EMA && ema != nullptr) {
+        #pragma unroll
+        for (int e = 0; e < 4; ++e) ev[e] = ema_update(ev[e], pv[e], d, omd);
+        *(float4*)(ema + i) = *(float4*)ev;
+      }
       if (w16 != nullptr) {
         if (half) {
           mthalfx4 o;
@@ -984,6 +1011,7 @@ __global__ void multi_tensor_sgd_kernel(MTTensorList tl, float lr, float mu,
                                         wd, c, rt);
     if (has_momentum) m[i] = mv;
     p[i] = pn;
+    if (EMA && ema != nullptr) ema[i] = ema_update(ema[i], pn, d, omd);
     if (w16 != nullptr) {
       if (half) ((_Float16*)w16)[i] = (_Float16)pn;
       else ((__bf16*)w16)[i] = (__bf16)pn;
@@ -1001,15 +1029,17 @@ struct MTMixedList {
   const __bf16* g[MT_MAX_TENSORS];
   float* w[MT_MAX_TENSORS];   // master
   float* m[MT_MAX_TENSORS];
+  float* ema[MT_MAX_TENSORS];   // average of the master, or null (EMA only)
   int size[MT_MAX_TENSORS];
   int ntensors;
-};
+};   // 5*256 + 128 + 4 = 1412 -> 1416 bytes of kernel-argument space
 
-template <bool SCALED>
+template <bool SCALED, bool EMA>
 __global__ void multi_tensor_sgd_o2_kernel(MTMixedList tl, float lr, float mu,
                                            float wd, bool has_momentum,
                                            const float* __restrict__ gscale,
-                                           const float* __restrict__ ratio) {
+                                           const float* __restrict__ ratio,
+                                           float d, float omd) {
   int t, start, end;
   if (!mt_locate(tl, t, start, end)) return;
   const float c = SCALED ? gscale[0] : 1.f;
@@ -1018,6 +1048,7 @@ __global__ void multi_tensor_sgd_o2_kernel(MTMixedList tl, float lr, float mu,
   const __bf16* g = tl.g[t];
   float* w = tl.w[t];
   float* m = has_momentum ? tl.m[t] : nullptr;
+  float* ema = EMA ? tl.ema[t] : nullptr;
   for (int i = start + threadIdx.x; i < end; i += blockDim.x) {
     float mv = 0.f;
     if (has_momentum) mv = m[i];
@@ -1026,7 +1057,43 @@ __global__ void multi_tensor_sgd_o2_kernel(MTMixedList tl, float lr, float mu,
     if (has_momentum) m[i] = mv;
     w[i] = nw;
     p[i] = (__bf16)nw;
+    if (EMA && ema != nullptr) ema[i] = ema_update(ema[i], nw, d, omd);
   }
+}
+
+// ---------------------------------------------------------------------------
+// ema[t] <- d*ema[t] + omd*src[t] for tensors the optimizer does not step
+// (the BatchNorm running statistics). fp32 both; float4s when both pointers
+// are 16-byte aligned, element by element otherwise and for the last
+// size % 4. src is not modified.
+// ---------------------------------------------------------------------------
+struct MTEmaList {
+  const float* src[MT_MAX_TENSORS];
+  float* ema[MT_MAX_TENSORS];
+  int size[MT_MAX_TENSORS];
+  int ntensors;
+};
+
+__global__ void multi_tensor_ema_kernel(MTEmaList tl, float d, float omd) {
+  int t, start, end;
+  if (!mt_locate(tl, t, start, end)) return;
+  const float* src = tl.src[t];
+  float* ema = tl.ema[t];
+  int tail = start;
+  if ((((size_t)src | (size_t)ema) & 15) == 0) {
+    // start is a multiple of MT_CHUNK, so every float4 below is aligned
+    tail = start + ((end - start) & ~3);
+    for (int i = start + 4 * threadIdx.x; i < tail; i += 4 * blockDim.x) {
+      float sv[4], ev[4];
+      *(float4*)sv = *(const float4*)(src + i);
+      *(float4*)ev = *(const float4*)(ema + i);
+      #pragma unroll
+      for (int e = 0; e < 4; ++e) ev[e] = ema_update(ev[e], sv[e], d, omd);
+      *(float4*)(ema + i) = *(float4*)ev;
+    }
+  }
+  for (int i = tail + threadIdx.x; i < end; i += blockDim.x)
+    ema[i] = ema_update(ema[i], src[i], d, omd);
 }
 
 // ---------------------------------------------------------------------------
@@ -2146,18 +2213,48 @@ struct MTBatch {
   }
 };
 
+typedef std::vector<c10::optional<at::Tensor>> OptTensors;
+
+// emas[i], where given, as float* for the list structs: fp32 in the layout of
+// `like` (the fp32 parameter or the O2 master), else null.
+static float* ema_ptr(const OptTensors& emas, size_t i, const at::Tensor& like,
+                      const char* who) {
+  if (emas.empty() || !emas[i].has_value()) return nullptr;
+  const at::Tensor& e = *emas[i];
+  TORCH_CHECK(e.is_cuda() && e.device() == like.device() &&
+              e.scalar_type() == at::kFloat && e.numel() == like.numel() &&
+              e.sizes() == like.sizes() && e.strides() == like.strides(),
+              who, ": ema must be float32 in the weight's layout");
+  return e.data_ptr<float>();
+}
+
+// The two floats every EMA kernel takes: d and 1 - d, formed once here.
+struct EmaDecay {
+  float d, omd;
+  explicit EmaDecay(double decay) : d((float)decay), omd(1.f - (float)decay) {
+    TORCH_CHECK(decay >= 0 && decay <= 1, "ema_decay must be in [0, 1], got ",
+                decay);
+  }
+};
+
 // gscale/ratio null: the plain kernel. Otherwise the scaled one, with
-// ratio[i] the coefficient of params[i].
+// ratio[i] the coefficient of params[i]. emas empty: no averages, and the
+// kernels launched are the ones without EMA.
 static void multi_tensor_sgd_impl(std::vector<at::Tensor>& params,
                                   std::vector<at::Tensor>& grads,
                                   std::vector<at::Tensor>& bufs,
                                   double lr, double momentum,
                                   double weight_decay,
                                   std::vector<c10::optional<at::Tensor>>& w16s,
-                                  const float* gscale, const float* ratio) {
+                                  const float* gscale, const float* ratio,
+                                  const OptTensors& emas, double ema_decay) {
   const bool has_momentum = !bufs.empty();
   const bool scaled = gscale != nullptr;
+  const bool ema = !emas.empty();
+  const EmaDecay dec(ema_decay);
   TORCH_CHECK(params.size() == grads.size());
+  TORCH_CHECK(!ema || emas.size() == params.size(),
+              "multi_tensor_sgd: one ema entry (or None) per param");
   TORCH_CHECK(!has_momentum || bufs.size() == params.size(),
               "multi_tensor_sgd: one momentum buffer per param");
   TORCH_CHECK(w16s.empty() || w16s.size() == params.size(),
@@ -2178,6 +2275,7 @@ static void multi_tensor_sgd_impl(std::vector<at::Tensor>& params,
       tl.p[t] = p.data_ptr<float>();
       tl.g[t] = grads[i].data_ptr<float>();
       tl.m[t] = has_momentum ? bufs[i].data_ptr<float>() : nullptr;
+      tl.ema[t] = ema_ptr(emas, i, p, "multi_tensor_sgd");
       tl.w16[t] = nullptr;
       tl.w16_half[t] = false;
       if (!w16s.empty() && w16s[i].has_value()) {
@@ -2192,11 +2290,15 @@ static void multi_tensor_sgd_impl(std::vector<at::Tensor>& params,
         tl.w16_half[t] = w16.scalar_type() == at::kHalf;
       }
     }
-    hipLaunchKernelGGL(scaled ? multi_tensor_sgd_kernel<true>
-                              : multi_tensor_sgd_kernel<false>,
+    auto kernel = ema ? (scaled ? multi_tensor_sgd_kernel<true, true>
+                                : multi_tensor_sgd_kernel<false, true>)
+                      : (scaled ? multi_tensor_sgd_kernel<true, false>
+                                : multi_tensor_sgd_kernel<false, false>);
+    hipLaunchKernelGGL(kernel,
                        dim3(b.nblocks), dim3(256), 0, stream, tl, (float)lr,
                        (float)momentum, (float)weight_decay, has_momentum,
-                       gscale, scaled ? ratio + first : nullptr);
+                       gscale, scaled ? ratio + first : nullptr, dec.d,
+                       dec.omd);
   }
 }
 
@@ -2204,9 +2306,10 @@ void multi_tensor_sgd(std::vector<at::Tensor> params,
                       std::vector<at::Tensor> grads,
                       std::vector<at::Tensor> bufs,
                       double lr, double momentum, double weight_decay,
-                      std::vector<c10::optional<at::Tensor>> w16s) {
+                      std::vector<c10::optional<at::Tensor>> w16s,
+                      OptTensors emas, double ema_decay) {
   multi_tensor_sgd_impl(params, grads, bufs, lr, momentum, weight_decay, w16s,
-                        nullptr, nullptr);
+                        nullptr, nullptr, emas, ema_decay);
 }
 
 // The two device coefficients of the scaled kernels: gscale [1], ratio [n].
@@ -2226,11 +2329,13 @@ void multi_tensor_sgd_scaled(std::vector<at::Tensor> params,
                              std::vector<at::Tensor> bufs,
                              double lr, double momentum, double weight_decay,
                              at::Tensor gscale, at::Tensor ratio,
-                             std::vector<c10::optional<at::Tensor>> w16s) {
+                             std::vector<c10::optional<at::Tensor>> w16s,
+                             OptTensors emas, double ema_decay) {
   if (params.empty()) return;
   check_coeffs(gscale, ratio, params.size(), params[0]);
   multi_tensor_sgd_impl(params, grads, bufs, lr, momentum, weight_decay, w16s,
-                        gscale.data_ptr<float>(), ratio.data_ptr<float>());
+                        gscale.data_ptr<float>(), ratio.data_ptr<float>(),
+                        emas, ema_decay);
 }
 
 static void multi_tensor_sgd_o2_impl(std::vector<at::Tensor>& params,
@@ -2239,11 +2344,17 @@ static void multi_tensor_sgd_o2_impl(std::vector<at::Tensor>& params,
                                      std::vector<at::Tensor>& bufs,
                                      double lr, double momentum,
                                      double weight_decay,
-                                     const float* gscale, const float* ratio) {
+                                     const float* gscale, const float* ratio,
+                                     const OptTensors& emas,
+                                     double ema_decay) {
   const bool has_momentum = !bufs.empty();
   const bool scaled = gscale != nullptr;
+  const bool ema = !emas.empty();
+  const EmaDecay dec(ema_decay);
   TORCH_CHECK(params.size() == grads.size() &&
               params.size() == masters.size());
+  TORCH_CHECK(!ema || emas.size() == params.size(),
+              "multi_tensor_sgd_o2: one ema entry (or None) per param");
   TORCH_CHECK(!has_momentum || bufs.size() == params.size(),
               "multi_tensor_sgd_o2: one momentum buffer per param");
   auto stream = cur_stream();
@@ -2267,12 +2378,17 @@ static void multi_tensor_sgd_o2_impl(std::vector<at::Tensor>& params,
       tl.g[t] = reinterpret_cast<const __bf16*>(grads[i].data_ptr());
       tl.w[t] = masters[i].data_ptr<float>();
       tl.m[t] = has_momentum ? bufs[i].data_ptr<float>() : nullptr;
+      tl.ema[t] = ema_ptr(emas, i, masters[i], "multi_tensor_sgd_o2");
     }
-    hipLaunchKernelGGL(scaled ? multi_tensor_sgd_o2_kernel<true>
-                              : multi_tensor_sgd_o2_kernel<false>,
+    auto kernel = ema ? (scaled ? multi_tensor_sgd_o2_kernel<true, true>
+                                : multi_tensor_sgd_o2_kernel<false, true>)
+                      : (scaled ? multi_tensor_sgd_o2_kernel<true, false>
+                                : multi_tensor_sgd_o2_kernel<false, false>);
+    hipLaunchKernelGGL(kernel,
                        dim3(b.nblocks), dim3(256), 0, stream, tl, (float)lr,
                        (float)momentum, (float)weight_decay, has_momentum,
-                       gscale, scaled ? ratio + first : nullptr);
+                       gscale, scaled ? ratio + first : nullptr, dec.d,
+                       dec.omd);
   }
 }
 
@@ -2280,9 +2396,10 @@ void multi_tensor_sgd_o2(std::vector<at::Tensor> params,
                          std::vector<at::Tensor> grads,
                          std::vector<at::Tensor> masters,
                          std::vector<at::Tensor> bufs,
-                         double lr, double momentum, double weight_decay) {
+                         double lr, double momentum, double weight_decay,
+                         OptTensors emas, double ema_decay) {
   multi_tensor_sgd_o2_impl(params, grads, masters, bufs, lr, momentum,
-                           weight_decay, nullptr, nullptr);
+                           weight_decay, nullptr, nullptr, emas, ema_decay);
 }
 
 void multi_tensor_sgd_o2_scaled(std::vector<at::Tensor> params,
@@ -2291,12 +2408,41 @@ void multi_tensor_sgd_o2_scaled(std::vector<at::Tensor> params,
                                 std::vector<at::Tensor> bufs,
                                 double lr, double momentum,
                                 double weight_decay,
-                                at::Tensor gscale, at::Tensor ratio) {
+                                at::Tensor gscale, at::Tensor ratio,
+                                OptTensors emas, double ema_decay) {
   if (params.empty()) return;
   check_coeffs(gscale, ratio, params.size(), params[0]);
   multi_tensor_sgd_o2_impl(params, grads, masters, bufs, lr, momentum,
                            weight_decay, gscale.data_ptr<float>(),
-                           ratio.data_ptr<float>());
+                           ratio.data_ptr<float>(), emas, ema_decay);
+}
+
+// emas[i] <- decay*emas[i] + (1 - decay)*srcs[i]; no allocation, no sync.
+void multi_tensor_ema(std::vector<at::Tensor> srcs,
+                      std::vector<at::Tensor> emas, double decay) {
+  TORCH_CHECK(srcs.size() == emas.size(), "multi_tensor_ema: one ema per src");
+  const EmaDecay dec(decay);
+  auto stream = cur_stream();
+  for (size_t i = 0; i < srcs.size();) {
+    MTBatch<MTEmaList> b;
+    for (; !b.full() && i < srcs.size(); ++i) {
+      auto& s = srcs[i];
+      auto& e = emas[i];
+      TORCH_CHECK(s.is_cuda() && s.is_non_overlapping_and_dense() &&
+                  s.scalar_type() == at::kFloat,
+                  "multi_tensor_ema expects dense fp32 sources");
+      TORCH_CHECK(e.is_cuda() && e.device() == s.device() &&
+                  e.scalar_type() == at::kFloat && e.sizes() == s.sizes() &&
+                  e.strides() == s.strides(),
+                  "multi_tensor_ema: ema must be float32 in the source's "
+                  "layout");
+      const int t = b.push(s.numel());
+      b.tl.src[t] = s.data_ptr<float>();
+      b.tl.ema[t] = e.data_ptr<float>();
+    }
+    hipLaunchKernelGGL(multi_tensor_ema_kernel, dim3(b.nblocks), dim3(256), 0,
+                       stream, b.tl, dec.d, dec.omd);
+  }
 }
 
 // sq[0][i] <- sum w_i^2, sq[1][i] <- sum g_i^2 for every tensor, through
@@ -2615,9 +2761,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "that receives the rounded new weight",
         py::arg("params"), py::arg("grads"), py::arg("bufs"), py::arg("lr"),
         py::arg("momentum"), py::arg("weight_decay"),
-        py::arg("w16s") = std::vector<c10::optional<at::Tensor>>());
+        py::arg("w16s") = OptTensors(), py::arg("emas") = OptTensors(),
+        py::arg("ema_decay") = 0.0);
   m.def("multi_tensor_sgd_o2", &multi_tensor_sgd_o2,
-        "fused SGD with bf16 params/grads + fp32 master (apex O2)");
+        "fused SGD with bf16 params/grads + fp32 master (apex O2); emas: "
+        "per-param fp32 average of the master (or None)",
+        py::arg("params"), py::arg("grads"), py::arg("masters"),
+        py::arg("bufs"), py::arg("lr"), py::arg("momentum"),
+        py::arg("weight_decay"), py::arg("emas") = OptTensors(),
+        py::arg("ema_decay") = 0.0);
+  m.def("multi_tensor_ema", &multi_tensor_ema,
+        "emas[i] <- decay*emas[i] + (1 - decay)*srcs[i], fp32, in one launch "
+        "per 32 tensors; srcs are not modified",
+        py::arg("srcs"), py::arg("emas"), py::arg("decay"));
   m.def("multi_tensor_sqnorm", &multi_tensor_sqnorm,
         "per-tensor sums of squares of w (fp32) and g (fp32|bf16) -> sq "
         "[2][n] through partials [2][>= chunks]; fixed order, no atomics",
@@ -2635,13 +2791,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "device memory; g is not modified",
         py::arg("params"), py::arg("grads"), py::arg("bufs"), py::arg("lr"),
         py::arg("momentum"), py::arg("weight_decay"), py::arg("gscale"),
-        py::arg("ratio"),
-        py::arg("w16s") = std::vector<c10::optional<at::Tensor>>());
+        py::arg("ratio"), py::arg("w16s") = OptTensors(),
+        py::arg("emas") = OptTensors(), py::arg("ema_decay") = 0.0);
   m.def("multi_tensor_sgd_o2_scaled", &multi_tensor_sgd_o2_scaled,
         "multi_tensor_sgd_o2 with d = ratio[t]*(gscale[0]*g + wd*master)",
         py::arg("params"), py::arg("grads"), py::arg("masters"),
         py::arg("bufs"), py::arg("lr"), py::arg("momentum"),
-        py::arg("weight_decay"), py::arg("gscale"), py::arg("ratio"));
+        py::arg("weight_decay"), py::arg("gscale"), py::arg("ratio"),
+        py::arg("emas") = OptTensors(), py::arg("ema_decay") = 0.0);
   m.def("multi_tensor_unscale", &multi_tensor_unscale,
         "multi-tensor grad unscale + inf/nan check");
   // ops/sgd.py keeps its own values for the CPU fallback; a test compares them

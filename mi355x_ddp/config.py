@@ -84,6 +84,9 @@ class TrainConfig:
     lars: bool = False
     lars_eta: float = 1e-3
     clip_grad_norm: float = 0.0
+    # exponential moving average of the weights and BatchNorm statistics,
+    # kept by the fused step and used for evaluation (core/ema.py); 0 = off
+    ema_decay: float = 0.0
 
     # native kernels
     native_ops: bool = True           # HIP kernels when extension present; fail loudly on GPU if absent
@@ -123,6 +126,9 @@ class TrainConfig:
         if self.clip_grad_norm < 0:
             raise ValueError("clip_grad_norm must be >= 0 (0 turns clipping "
                              f"off), got {self.clip_grad_norm}")
+        if not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError("ema_decay must be in [0, 1) (0 turns the "
+                             f"weight average off), got {self.ema_decay}")
 
     def per_rank_batch(self, world_size: int) -> int:
         return max(1, self.batch_size // max(1, world_size))
@@ -199,6 +205,10 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--clip_grad_norm", default=None, type=float,
                    help="clip gradients to this global L2 norm inside the "
                         "fused SGD step; 0 = off")
+    p.add_argument("--ema_decay", default=None, type=float,
+                   help="decay of the weight average kept by the fused SGD "
+                        "step, in [0, 1); evaluation and the best checkpoint "
+                        "then use the averaged weights; 0 = off")
     return p
 
 
@@ -243,7 +253,7 @@ def config_from_args(args: argparse.Namespace, **overrides) -> TrainConfig:
     if getattr(args, "lars", False):
         kw["lars"] = True
     for name in ("label_smoothing", "cutmix_alpha", "cutmix_prob",
-                 "lars_eta", "clip_grad_norm"):
+                 "lars_eta", "clip_grad_norm", "ema_decay"):
         if getattr(args, name, None) is not None:
             kw[name] = getattr(args, name)
     kw.update(overrides)

@@ -2,7 +2,8 @@
 tutorials/2.:89-95 'save only on rank 0', dead save_epoch knob utils/config.py:7).
 
 Layout: ckpts/{arch}_epoch{E}.pt and ckpts/{arch}_last.pt containing
-{epoch, model (unwrapped module state), optimizer, scheduler, scaler, best_acc}.
+{epoch, model (unwrapped module state), optimizer, scheduler, scaler, best_acc}
+and, in a run with --ema_decay, ema (WeightEMA.state_dict(): the averaged model).
 """
 from __future__ import annotations
 
@@ -33,6 +34,11 @@ def save_checkpoint(ckpt_dir: str, arch: str, epoch: int, model, optimizer=None,
         "scaler": scaler.state_dict() if scaler is not None else None,
         "best_acc": best_acc,
     }
+    # the averaged model of an --ema_decay run (core/ema.py), in the model's
+    # key layout; its parameter averages are optimizer state as well
+    ema = getattr(optimizer, "weight_ema", None)
+    if ema is not None:
+        state["ema"] = ema.state_dict()
     path = os.path.join(ckpt_dir, f"{arch}_{tag or f'epoch{epoch}'}.pt")
     torch.save(state, path)
     # {arch}_last.pt is a hardlink to the tagged file — one serialisation
@@ -54,6 +60,15 @@ def load_checkpoint(path: str, model, optimizer=None, scheduler=None,
     _unwrap(model).load_state_dict(state["model"])
     if optimizer is not None and state.get("optimizer"):
         optimizer.load_state_dict(state["optimizer"])
+    ema = getattr(optimizer, "weight_ema", None)
+    if ema is not None:
+        if state.get("ema"):
+            ema.load_state_dict(state["ema"])
+        else:
+            # a checkpoint without averages: they start from what was loaded
+            # (the parameter averages at the next step, in FusedSGD, whose
+            # load_state_dict keeps the run's own ema_decay)
+            ema.reset_buffers()
     if scheduler is not None and state.get("scheduler"):
         scheduler.load_state_dict(state["scheduler"])
     if scaler is not None and state.get("scaler"):

@@ -153,8 +153,10 @@ def train_one_epoch(model, loader, criterion, optimizer, epoch: int,
 
 @torch.no_grad()
 def validate(model, loader, criterion, device, cfg: TrainConfig,
-             sink: Optional[JsonlSink] = None, epoch: int = -1) -> float:
-    """Distributed evaluation (reference utils/validation.py:7-52)."""
+             sink: Optional[JsonlSink] = None, epoch: int = -1,
+             weights: Optional[str] = None) -> float:
+    """Distributed evaluation (reference utils/validation.py:7-52). `weights`
+    names the weight set in the `val` record when it is not the model's own."""
     model.eval()
     nprocs = dist_utils.get_world_size()
     batch_time = AverageMeter("Time", ":6.3f")
@@ -189,9 +191,22 @@ def validate(model, loader, criterion, device, cfg: TrainConfig,
     if dist_utils.is_main_process():
         print(f" * Acc@1 {top1.avg:.3f} Acc@5 {top5.avg:.3f}", flush=True)
         if sink is not None:
+            extra = {} if weights is None else {"weights": weights}
             sink.log(kind="val", epoch=epoch, loss=losses.avg,
-                     acc1=top1.avg, acc5=top5.avg)
+                     acc1=top1.avg, acc5=top5.avg, **extra)
     return top1.avg
+
+
+def validate_with(ema, model, loader, criterion, device, cfg: TrainConfig,
+                  sink: Optional[JsonlSink] = None, epoch: int = -1) -> float:
+    """`validate` on the averaged weights of `ema` (a core.ema.WeightEMA),
+    swapped in for the evaluation; with `ema` None, plain `validate`."""
+    if ema is None:
+        return validate(model, loader, criterion, device, cfg, sink=sink,
+                        epoch=epoch)
+    with ema.swapped():
+        return validate(model, loader, criterion, device, cfg, sink=sink,
+                        epoch=epoch, weights="ema")
 
 
 def fit(model, train_loader, test_loader, train_sampler, criterion, optimizer,
@@ -216,8 +231,11 @@ def fit(model, train_loader, test_loader, train_sampler, criterion, optimizer,
             if sink is not None:
                 sink.log(kind="epoch", epoch=epoch, seconds=epoch_s)
         if cfg.eval_every_epoch:
-            acc = validate(model, test_loader, criterion, device, cfg,
-                           sink=sink, epoch=epoch)
+            # with --ema_decay the averaged weights are what is evaluated, so
+            # best_acc and the best checkpoint follow them
+            acc = validate_with(getattr(optimizer, "weight_ema", None), model,
+                                test_loader, criterion, device, cfg,
+                                sink=sink, epoch=epoch)
             # >= so the first evaluation (possibly 0.0 on tiny synthetic
             # runs) still produces a best checkpoint
             if acc >= best_acc:

@@ -84,7 +84,13 @@ def build_training(cfg: TrainConfig, device: torch.device, world_size: int,
     optimizer = FusedSGD(model.parameters(), lr=cfg.lr, momentum=cfg.momentum,
                          weight_decay=cfg.weight_decay, lars=cfg.lars,
                          lars_eta=cfg.lars_eta,
-                         clip_grad_norm=cfg.clip_grad_norm)
+                         clip_grad_norm=cfg.clip_grad_norm,
+                         ema_decay=cfg.ema_decay)
+    if cfg.ema_decay > 0:
+        from .ema import WeightEMA
+        # reached through the optimizer by fit, validate-only runs and the
+        # checkpoint functions; the returned tuple stays what it was
+        optimizer.weight_ema = WeightEMA(model, optimizer)
     scheduler = build_scheduler(optimizer, cfg)
     scaler = build_scaler(cfg.amp)
     return model, criterion, optimizer, scheduler, scaler
@@ -132,8 +138,9 @@ def main_worker(local_rank: int, nprocs: int, cfg: TrainConfig,
     train_loader, test_loader, train_sampler = build_loaders(
         cfg, nprocs, rank, distributed=nprocs > 1, device=device)
     if cfg.evaluate:
-        from .engine import validate
-        best = validate(model, test_loader, criterion, device, cfg)
+        from .engine import validate_with
+        best = validate_with(getattr(optimizer, "weight_ema", None), model,
+                             test_loader, criterion, device, cfg)
         dist_utils.cleanup()
         return best
     best = fit(model, train_loader, test_loader, train_sampler, criterion,

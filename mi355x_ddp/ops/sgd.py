@@ -50,6 +50,24 @@ sync, no host-to-device copy and no allocation, so it captures into a
 hipGraph. The norm is global over all param groups; max_norm, eta and wd are
 each group's own. The effect of either feature on accuracy has not been
 measured in this project.
+
+Weight EMA (``ema_decay=d``, 0 < d < 1; 0, the default, is off, and then the
+step is exactly the one above, same code path and same launches). Every
+stepped tensor keeps an fp32 average ``state[p]["ema"]`` of its fp32 weight w
+(the parameter, or the O2 master), created at the first step as a copy of w
+before that step's update (timm's ``ModelEmaV2`` initialisation) and then, in
+the same kernel that produces the new weight,
+
+    e <- d*e + (1 - d)*w_new          fmaf(d, e, omd*w_new), omd = 1.f - d
+
+with d and omd rounded to fp32 once on the host. Tensors the optimizer does
+not step (the BatchNorm running statistics) are averaged by the same formula
+when handed over with `track_buffers`: one `multi_tensor_ema` launch per 32
+tensors at the end of `step()`, so a skipped fp16 step skips the averages too
+and a captured step holds them. core/ema.py (`WeightEMA`) swaps the averages
+in for evaluation. Out of scope: decay warm-up or schedules, updating every N
+steps, evaluating both weight sets per epoch. The effect on accuracy has not
+been measured in this project.
 """
 from __future__ import annotations
 
@@ -85,6 +103,34 @@ class _NormBuffers:
         self.excluded = torch.tensor(excluded, dtype=torch.uint8).to(dev)
 
 
+def ema_coeffs(decay: float):
+    """(d, omd) as the kernels take them: d rounded to fp32, omd = 1 - d formed
+    in fp32, both returned as Python floats that fp32 holds exactly."""
+    d = torch.tensor(float(decay), dtype=torch.float32)
+    return float(d), float(torch.ones((), dtype=torch.float32) - d)
+
+
+def ema_update_torch(emas, ws, decay: float) -> None:
+    """e <- d*e + (1 - d)*w in torch for every pair, fp32; a None average is
+    skipped. The kernels' formula (they fuse the multiply-add)."""
+    d, omd = ema_coeffs(decay)
+    for e, w in zip(emas, ws):
+        if e is not None:
+            e.mul_(d).add_(w, alpha=omd)
+
+
+def multi_tensor_ema(srcs: List[torch.Tensor], emas: List[torch.Tensor],
+                     decay: float) -> None:
+    """emas[i] <- decay*emas[i] + (1 - decay)*srcs[i], fp32: one native launch
+    per 32 tensors on the GPU, torch on the CPU."""
+    if not srcs:
+        return
+    if _backend.native_enabled(srcs[0]):
+        _backend.C().multi_tensor_ema(srcs, emas, decay)
+    else:
+        ema_update_torch(emas, srcs, decay)
+
+
 def _group_scaled(group) -> bool:
     return bool(group.get("lars", False)) or \
         group.get("clip_grad_norm", 0.0) > 0
@@ -93,7 +139,11 @@ def _group_scaled(group) -> bool:
 class FusedSGD(torch.optim.Optimizer):
     def __init__(self, params, lr: float, momentum: float = 0.0,
                  weight_decay: float = 0.0, lars: bool = False,
-                 lars_eta: float = 1e-3, clip_grad_norm: float = 0.0):
+                 lars_eta: float = 1e-3, clip_grad_norm: float = 0.0,
+                 ema_decay: float = 0.0):
+        if not 0 <= ema_decay < 1:
+            raise ValueError("ema_decay must be in [0, 1) (0 turns the weight "
+                             f"average off), got {ema_decay}")
         if lars_eta <= 0:
             raise ValueError(f"lars_eta must be > 0, got {lars_eta}")
         if clip_grad_norm < 0:
@@ -101,10 +151,76 @@ class FusedSGD(torch.optim.Optimizer):
                              f"off), got {clip_grad_norm}")
         defaults = dict(lr=lr, momentum=momentum, weight_decay=weight_decay,
                         lars=bool(lars), lars_eta=lars_eta,
-                        clip_grad_norm=clip_grad_norm)
+                        clip_grad_norm=clip_grad_norm,
+                        ema_decay=float(ema_decay))
         super().__init__(params, defaults)
         self._norm: Optional[_NormBuffers] = None
         self._grad_norm: Optional[torch.Tensor] = None
+        self._ema_buffers = ([], [])
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.__dict__.setdefault("_ema_buffers", ([], []))
+        # a state dict saved before ema_decay existed has no such key in its
+        # groups: the run's own setting holds, so its averages start from the
+        # loaded weights
+        for group in self.param_groups:
+            group.setdefault("ema_decay", self.defaults.get("ema_decay", 0.0))
+
+    def load_state_dict(self, state_dict) -> None:
+        """torch's, with two differences.
+
+        `ema_decay` stays this run's own in every group, whatever the saved
+        groups hold (0, another value, or no such key): whether a run averages
+        is its `--ema_decay`, and a `WeightEMA` built for the run relies on it.
+        The saved averages are restored either way; a run with averages that
+        loads a state without them starts them, at its next step, from the
+        loaded weights.
+
+        The fp32 state of a bf16 (O2) parameter stays fp32: torch casts every
+        floating-point state tensor to the parameter's dtype, which would
+        round `master`, `momentum_buffer` and `ema` to bf16."""
+        own = [g.get("ema_decay", 0.0) for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for group, decay in zip(self.param_groups, own):
+            group["ema_decay"] = decay
+        saved = state_dict["state"]
+        for group, sgroup in zip(self.param_groups,
+                                 state_dict["param_groups"]):
+            for p, pid in zip(group["params"], sgroup["params"]):
+                if p.dtype != torch.bfloat16 or pid not in saved:
+                    continue
+                for key in ("master", "momentum_buffer", "ema"):
+                    if key in saved[pid]:
+                        self.state[p][key] = saved[pid][key].detach().to(
+                            device=p.device, dtype=torch.float32, copy=True)
+
+    def _buffer_decay(self) -> float:
+        """The decay of the tracked buffers: the one every group has."""
+        decays = {g.get("ema_decay", 0.0) for g in self.param_groups}
+        if len(decays) != 1 or min(decays) <= 0:
+            raise RuntimeError(
+                "track_buffers needs one ema_decay > 0 shared by every param "
+                f"group, got {sorted(decays)}")
+        return decays.pop()
+
+    def track_buffers(self, pairs) -> None:
+        """`pairs`: (buffer, ema_buffer) fp32 tensors that no group steps (the
+        BatchNorm running statistics). Every `step()` that runs averages them
+        after the parameter update, with the groups' `ema_decay`, which has to
+        be one positive value for all groups (checked here and at every step
+        that has buffers to average); replaces any earlier list."""
+        srcs, emas = [], []
+        for src, ema in pairs:
+            if src.dtype != torch.float32 or ema.dtype != torch.float32 or \
+                    src.shape != ema.shape or src.device != ema.device:
+                raise ValueError("track_buffers takes (buffer, ema_buffer) "
+                                 "pairs of fp32 tensors of one shape")
+            srcs.append(src)
+            emas.append(ema)
+        if srcs:
+            self._buffer_decay()
+        self._ema_buffers = (srcs, emas)
 
     def grad_norm(self) -> Optional[torch.Tensor]:
         """0-dim tensor on the parameters' device: the global gradient norm of
@@ -143,7 +259,21 @@ class FusedSGD(torch.optim.Optimizer):
                 ms.append(state["momentum_buffer"])
         if not has_momentum:
             m32 = m16 = None
-        return _Gathered(p32, g32, m32, s32, p16, g16, w16, m16)
+        # a pass of its own, so that the loop above costs a step without
+        # averages nothing
+        e32 = e16 = None
+        if group.get("ema_decay", 0.0) > 0:
+            e32 = [self._ema_of(p, p) for p in p32]
+            e16 = [self._ema_of(p, w) for p, w in zip(p16, w16)]
+        return _Gathered(p32, g32, m32, s32, p16, g16, w16, m16, e32, e16)
+
+    def _ema_of(self, p, w) -> torch.Tensor:
+        """The average of parameter p's fp32 weight w; at first use a copy of
+        w, which `_gather` sees before the step's update."""
+        state = self.state[p]
+        if "ema" not in state:
+            state["ema"] = w.detach().clone()
+        return state["ema"]
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -156,6 +286,9 @@ class FusedSGD(torch.optim.Optimizer):
         else:
             for group in self.param_groups:
                 _step_group(group, self._gather(group))
+        srcs, emas = self._ema_buffers
+        if srcs:
+            multi_tensor_ema(srcs, emas, self._buffer_decay())
         return loss
 
     def _step_scaled(self) -> None:
@@ -220,6 +353,10 @@ class _Gathered(NamedTuple):
     g16: list
     w16: list
     m16: Optional[list]
+    # fp32 averages of p32 and of the masters w16; None when the group's
+    # ema_decay is 0
+    e32: Optional[list] = None
+    e16: Optional[list] = None
 
 
 def _step_group(group, got: _Gathered, gscale=None, ratio32=None,
@@ -227,12 +364,13 @@ def _step_group(group, got: _Gathered, gscale=None, ratio32=None,
     """Steps one group; without `gscale` and the ratios, the plain step."""
     lr, momentum = group["lr"], group["momentum"]
     wd = group["weight_decay"]
+    decay = group.get("ema_decay", 0.0)
     if got.p32:
         fused_sgd_step(got.p32, got.g32, got.m32, lr, momentum, wd, got.s32,
-                       gscale, ratio32)
+                       gscale, ratio32, got.e32, decay)
     if got.p16:
         fused_sgd_o2_step(got.p16, got.g16, got.w16, got.m16, lr, momentum,
-                          wd, gscale, ratio16)
+                          wd, gscale, ratio16, got.e16, decay)
 
 
 def sgd_coeffs_torch(sq_w: torch.Tensor, sq_g: torch.Tensor,
@@ -259,10 +397,12 @@ def sgd_coeffs_torch(sq_w: torch.Tensor, sq_g: torch.Tensor,
 
 
 def _update_torch(ws, grads, momentum_bufs, lr, momentum, weight_decay,
-                  gscale, ratio, params16=None) -> None:
+                  gscale, ratio, params16=None, emas=None,
+                  ema_decay: float = 0.0) -> None:
     """The update in torch, same math (used on CPU and for parity tests), on
     the fp32 weights `ws`. With `params16` (the O2 path) `ws` are the masters
-    of bf16 parameters, which get the rounded copy."""
+    of bf16 parameters, which get the rounded copy. With `emas` (one fp32
+    average or None per weight) the new weights are averaged into them."""
     for i, (w, g) in enumerate(zip(ws, grads)):
         if params16 is not None:
             g = g.float()
@@ -277,6 +417,8 @@ def _update_torch(ws, grads, momentum_bufs, lr, momentum, weight_decay,
         w.add_(g, alpha=-lr)
         if params16 is not None:
             params16[i].copy_(w)
+    if emas:
+        ema_update_torch(emas, ws, ema_decay)
 
 
 def fused_sgd_step(params: List[torch.Tensor], grads: List[torch.Tensor],
@@ -284,12 +426,17 @@ def fused_sgd_step(params: List[torch.Tensor], grads: List[torch.Tensor],
                    lr: float, momentum: float, weight_decay: float,
                    shadows: Optional[List[Optional[WeightShadow]]] = None,
                    gscale: Optional[torch.Tensor] = None,
-                   ratio: Optional[torch.Tensor] = None) -> None:
+                   ratio: Optional[torch.Tensor] = None,
+                   emas: Optional[List[Optional[torch.Tensor]]] = None,
+                   ema_decay: float = 0.0) -> None:
     """`shadows[i]` is params[i]'s WeightShadow or None. Each one is either
     rewritten with the new weight here (native path) or invalidated.
 
     With `gscale` ([1]) and `ratio` ([len(params)]) the update is the scaled
-    one, d = ratio[i]*(gscale*g + wd*p); the gradients are not modified."""
+    one, d = ratio[i]*(gscale*g + wd*p); the gradients are not modified.
+
+    With `emas` (one fp32 average or None per param) the same launch does
+    emas[i] <- ema_decay*emas[i] + (1 - ema_decay)*p_new."""
     live = []
     for p, sh in zip(params, shadows or ()):
         if sh is None:
@@ -302,7 +449,8 @@ def fused_sgd_step(params: List[torch.Tensor], grads: List[torch.Tensor],
         for _, sh in live:
             sh.invalidate()
         _update_torch(params, grads, momentum_bufs, lr, momentum,
-                      weight_decay, gscale, ratio)
+                      weight_decay, gscale, ratio, emas=emas,
+                      ema_decay=ema_decay)
         return
     w16s = []
     if live:
@@ -310,13 +458,16 @@ def fused_sgd_step(params: List[torch.Tensor], grads: List[torch.Tensor],
         w16s = [sh.w16 if sh is not None and id(sh) in keep else None
                 for sh in shadows]
     bufs = momentum_bufs if momentum_bufs is not None else []
+    # no averages: the call, and so the kernel, of a step without them
+    ema_kw = dict(emas=emas, ema_decay=ema_decay) if emas else {}
     if gscale is None:
         _backend.C().multi_tensor_sgd(params, grads, bufs,
-                                      lr, momentum, weight_decay, w16s)
+                                      lr, momentum, weight_decay, w16s,
+                                      **ema_kw)
     else:
         _backend.C().multi_tensor_sgd_scaled(params, grads, bufs,
                                              lr, momentum, weight_decay,
-                                             gscale, ratio, w16s)
+                                             gscale, ratio, w16s, **ema_kw)
     if live:
         _backend.C().multi_tensor_build_wT([sh.w16 for _, sh in live],
                                            [sh.wT for _, sh in live])
@@ -329,18 +480,24 @@ def fused_sgd_o2_step(params: List[torch.Tensor], grads: List[torch.Tensor],
                       momentum_bufs: Optional[List[torch.Tensor]],
                       lr: float, momentum: float, weight_decay: float,
                       gscale: Optional[torch.Tensor] = None,
-                      ratio: Optional[torch.Tensor] = None) -> None:
+                      ratio: Optional[torch.Tensor] = None,
+                      emas: Optional[List[Optional[torch.Tensor]]] = None,
+                      ema_decay: float = 0.0) -> None:
     """bf16 params/grads, fp32 master + momentum (apex-O2 update); scaled as
-    in fused_sgd_step when `gscale` and `ratio` are given."""
+    in fused_sgd_step when `gscale` and `ratio` are given. `emas` average the
+    new masters."""
     if not (params and _backend.native_enabled(params[0])):
         _update_torch(masters, grads, momentum_bufs, lr, momentum,
-                      weight_decay, gscale, ratio, params16=params)
+                      weight_decay, gscale, ratio, params16=params,
+                      emas=emas, ema_decay=ema_decay)
         return
     bufs = momentum_bufs if momentum_bufs is not None else []
+    ema_kw = dict(emas=emas, ema_decay=ema_decay) if emas else {}
     if gscale is None:
         _backend.C().multi_tensor_sgd_o2(
-            params, grads, masters, bufs, lr, momentum, weight_decay)
+            params, grads, masters, bufs, lr, momentum, weight_decay,
+            **ema_kw)
     else:
         _backend.C().multi_tensor_sgd_o2_scaled(
             params, grads, masters, bufs, lr, momentum, weight_decay,
-            gscale, ratio)
+            gscale, ratio, **ema_kw)

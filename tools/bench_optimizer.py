@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""What LARS and gradient-norm clipping cost in the optimizer step.
+"""What LARS, gradient-norm clipping and the weight EMA cost in the optimizer
+step.
 
 Times FusedSGD.step() alone, on one GPU, on the parameter sets of ResNet-18
 and ResNet-50 (fp32, channels_last, momentum 0.9, weight decay 1e-4) with
@@ -9,6 +10,9 @@ random gradients. Variants:
   clip    clip_grad_norm on
   lars    LARS on
   both    both on
+  ema          the weight average fused into the step (ema_decay 0.999)
+  ema_foreach  the plain step, then torch._foreach_lerp_ over the same
+               tensors: what the fused average replaces, and its yardstick
 
 each also with bf16 conv weight shadows live ("+shadows": the step then
 stores the rounded weights and rotates them, as it does under --amp bf16).
@@ -25,7 +29,8 @@ The learning rate is 1e-9 so that hundreds of steps on the same gradients
 leave the weights where they are; the arithmetic does not depend on it.
 
 Usage: python tools/bench_optimizer.py [--archs resnet18,resnet50]
-           [--variants plain,clip,lars,both] [--steps 200] [--repeats 5]
+           [--variants plain,clip,lars,both,ema,ema_foreach] [--steps 200]
+           [--repeats 5]
 """
 import argparse
 import json
@@ -47,13 +52,30 @@ FEATURES = {
     "clip": dict(clip_grad_norm=1.0),
     "lars": dict(lars=True),
     "both": dict(lars=True, clip_grad_norm=1.0),
+    "ema": dict(ema_decay=0.999),
+    "ema_foreach": {},
 }
+EMA_DECAY = 0.999
+
+
+class StepThenLerp:
+    """The plain fused step followed by the per-tensor average in torch."""
+
+    def __init__(self, opt, params):
+        self.opt = opt
+        self.params = [p.detach() for p in params]
+        self.emas = [p.detach().clone() for p in params]
+
+    def step(self):
+        self.opt.step()
+        torch._foreach_lerp_(self.emas, self.params, 1.0 - EMA_DECAY)
 
 
 def parse_args():
     p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     p.add_argument("--archs", default="resnet18,resnet50")
-    p.add_argument("--variants", default="plain,clip,lars,both")
+    p.add_argument("--variants",
+                   default="plain,clip,lars,both,ema,ema_foreach")
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
     p.add_argument("--repeats", type=int, default=5)
@@ -122,6 +144,8 @@ def main():
                 # momentum buffers
                 opts[name] = FusedSGD(params, lr=1e-9, momentum=0.9,
                                       weight_decay=1e-4, **FEATURES[name])
+                if name == "ema_foreach":
+                    opts[name] = StepThenLerp(opts[name], params)
             counts = {}
             for name, opt in opts.items():
                 for _ in range(args.warmup):
