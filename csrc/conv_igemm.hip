@@ -148,15 +148,36 @@ template <int NF>
 __device__ __forceinline__ void store_frag_slab(float* __restrict__ dwp,
                                                 const f32x4* acc, int tid);
 
+// BNEPI (MODE 0 only): the evaluation-mode epilogue. BatchNorm in eval mode
+// is a per-channel affine map, so the conv applies it to the fp32 accumulator
+// it still holds, adds the residual, clamps and rounds ONCE:
+//   out = round(relu(fma(acc, scale[n], shift[n]) + res[m][n]))
+// scale/shift are fp32 [N]; res is null or an [M][N] tensor of the output's
+// dtype; fmaxf drops a NaN as bn_fwd_vec_kernel does. The plain kernels take
+// an empty struct in its place and compile as they did without it.
+struct NoEpi {};
+template <typename T> struct BnEpi {
+  const float* scale;
+  const float* shift;
+  const T* res;
+  int relu;
+};
+template <typename T, bool BNEPI> struct EpiArg { typedef NoEpi type; };
+template <typename T> struct EpiArg<T, true> { typedef BnEpi<T> type; };
+
 template <typename T, int MODE, bool FAST, int BMT = BM, bool PADC = false,
-          int BNT = BN, bool SPLITK = false>
+          int BNT = BN, bool SPLITK = false, bool BNEPI = false>
 __global__ __launch_bounds__(256)
 void conv_igemm_kernel(const T* __restrict__ Ag,
                        const T* __restrict__ Bg,
-                       T* __restrict__ out, ConvDims d) {
+                       T* __restrict__ out, ConvDims d,
+                       typename EpiArg<T, BNEPI>::type ep) {
   static_assert(!SPLITK || (FAST && MODE != 2 && !PADC && BMT == 128 &&
                             BNT == 128),
                 "split-K exists for the pipelined 128x128 tile only");
+  static_assert(!BNEPI || (MODE == 0 && !SPLITK),
+                "the BN epilogue is a forward epilogue; split-K applies it in "
+                "the reduce");
   typedef typename Elem16<T>::x8 x8;
   constexpr int MI = BMT / 32;
   constexpr int NI = BNT / 32;
@@ -395,6 +416,18 @@ void conv_igemm_kernel(const T* __restrict__ Ag,
   // ---- epilogue: D row = (lane>>4)*4 + reg, col = lane&15 ----------------
   const int dm = (lane >> 4) * 4;
   const int dn = lane & 15;
+  // BNEPI: a lane's column is fixed per N-tile, so its two coefficients load
+  // once per N-tile here (a column past N reads the last one and stores
+  // nothing)
+  float sc[BNEPI ? NI : 1], sh[BNEPI ? NI : 1];
+  if constexpr (BNEPI) {
+    #pragma unroll
+    for (int ni = 0; ni < NI; ++ni) {
+      const int n = min(n0 + wn + ni * 16 + dn, d.N - 1);
+      sc[ni] = ep.scale[n];
+      sh[ni] = ep.shift[n];
+    }
+  }
   #pragma unroll
   for (int mi = 0; mi < MI; ++mi) {
     #pragma unroll
@@ -411,7 +444,14 @@ void conv_igemm_kernel(const T* __restrict__ Ag,
           decode_m2(m, d, pa, pb, on, ooh, oow);
           om = ((long)on * d.OH + ooh) * d.OW + oow;
         }
-        out[om * d.N + n] = Elem16<T>::from_float(acc[mi][ni][r]);
+        if constexpr (BNEPI) {
+          float v = fmaf(acc[mi][ni][r], sc[ni], sh[ni]);
+          if (ep.res != nullptr) v += (float)ep.res[om * d.N + n];
+          if (ep.relu) v = fmaxf(v, 0.f);
+          out[om * d.N + n] = Elem16<T>::from_float(v);
+        } else {
+          out[om * d.N + n] = Elem16<T>::from_float(acc[mi][ni][r]);
+        }
       }
     }
   }
@@ -1179,11 +1219,16 @@ void wgrad_reduce_frag_kernel(const float* __restrict__ part,
 // wm = (wave >> 1) * 64, wn = (wave & 1) * 64, f = mi * 4 + ni, row =
 // (lane >> 4) * 4 + reg, col = lane & 15). Rows / columns past M / N (edge
 // tiles) are dropped; N % 8 != 0 stores element by element.
-template <typename T>
+// BNEPI: the evaluation epilogue of conv_igemm_kernel, applied to the summed
+// value before the one rounding. The thread's 8 channels take two float4 of
+// scale and of shift, and each row one 16-byte residual load at the address
+// of the store it precedes; the N % 8 != 0 tail reads element by element.
+template <typename T, bool BNEPI = false>
 __global__ __launch_bounds__(256)
 void igemm_reduce_frag_kernel(const float* __restrict__ part,
                               T* __restrict__ out, int M, int N, int tn,
-                              long nslots, int splits) {
+                              long nslots, int splits,
+                              typename EpiArg<T, BNEPI>::type ep) {
   typedef typename Elem16<T>::x8 x8;
   const long u = (long)blockIdx.x * 256 + threadIdx.x;  // grid = 2 * ntiles
   const int tile = (int)(u >> 9);
@@ -1222,6 +1267,49 @@ void igemm_reduce_frag_kernel(const float* __restrict__ part,
   const int n = bx * 128 + co * 8;
   if (n >= N) return;
   const bool vec = (N & 7) == 0;   // then n + 8 <= N and rows are 16 B aligned
+  if constexpr (BNEPI) {
+    float sc[8], sh[8];
+    if (vec) {
+      *(float4*)&sc[0] = *(const float4*)(ep.scale + n);
+      *(float4*)&sc[4] = *(const float4*)(ep.scale + n + 4);
+      *(float4*)&sh[0] = *(const float4*)(ep.shift + n);
+      *(float4*)&sh[4] = *(const float4*)(ep.shift + n + 4);
+    } else {
+      #pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int nj = min(n + j, N - 1);
+        sc[j] = ep.scale[nj];
+        sh[j] = ep.shift[nj];
+      }
+    }
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (m + r >= M) continue;
+      const long o = (long)(m + r) * N + n;
+      if (vec) {
+        x8 rv = {}, v;
+        if (ep.res != nullptr) rv = *(const x8*)(ep.res + o);
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float f = fmaf(s[j][r], sc[j], sh[j]);
+          if (ep.res != nullptr) f += (float)rv[j];
+          if (ep.relu) f = fmaxf(f, 0.f);
+          v[j] = Elem16<T>::from_float(f);
+        }
+        *(x8*)(out + o) = v;
+      } else {
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if (n + j >= N) continue;
+          float f = fmaf(s[j][r], sc[j], sh[j]);
+          if (ep.res != nullptr) f += (float)ep.res[o + j];
+          if (ep.relu) f = fmaxf(f, 0.f);
+          out[o + j] = Elem16<T>::from_float(f);
+        }
+      }
+    }
+    return;
+  }
   #pragma unroll
   for (int r = 0; r < 4; ++r) {
     if (m + r >= M) continue;
@@ -1566,9 +1654,10 @@ inline int igemm_splits(const ConvDims& d, long splits) {
 // One split-K launch + one reduce. The slabs are whole tiles in fragment
 // order (see store_frag_slab), allocated from the caching allocator on the
 // conv stream, so a hipGraph capture of the step still works.
-template <typename T, int MODE>
+template <typename T, int MODE, bool BNEPI = false>
 void igemm_splitk_launch(const at::Tensor& a, const at::Tensor& b,
-                         at::Tensor& out, const ConvDims& d, int splits) {
+                         at::Tensor& out, const ConvDims& d, int splits,
+                         typename EpiArg<T, BNEPI>::type ep = {}) {
   auto stream = conv_stream();
   const int tn = (d.N + 127) / 128, tm = (d.M + 127) / 128;
   const long nslots = (long)tm * tn * 4096;   // f32x4 per slice
@@ -1577,18 +1666,22 @@ void igemm_splitk_launch(const at::Tensor& a, const at::Tensor& b,
   hipLaunchKernelGGL(
       (conv_igemm_kernel<T, MODE, true, 128, false, 128, true>),
       dim3(tn, tm, splits), dim3(256), 0, stream, ptr16<T>(a), ptr16<T>(b),
-      reinterpret_cast<T*>(part.data_ptr()), d);
-  hipLaunchKernelGGL(igemm_reduce_frag_kernel<T>, dim3(2 * tm * tn), dim3(256),
-                     0, stream, part.data_ptr<float>(),
+      reinterpret_cast<T*>(part.data_ptr()), d, NoEpi{});
+  hipLaunchKernelGGL((igemm_reduce_frag_kernel<T, BNEPI>), dim3(2 * tm * tn),
+                     dim3(256), 0, stream, part.data_ptr<float>(),
                      reinterpret_cast<T*>(out.data_ptr()), d.M, d.N, tn,
-                     nslots, splits);
+                     nslots, splits, ep);
 }
 
 // The three passes are written once over the element type T; the public
 // wrappers below check the operands and pick T from their (shared) dtype.
-template <typename T>
+// BNEPI: the same launches with the evaluation epilogue (conv_fwd_bn_igemm);
+// `ep` then holds the checked coefficient and residual pointers.
+template <typename T, bool BNEPI = false>
 at::Tensor conv_fwd_igemm_t(at::Tensor x, at::Tensor w, long stride, long pad,
-                            long tile, long splits) {
+                            long tile, long splits,
+                            typename EpiArg<T, BNEPI>::type ep = {},
+                            const at::Tensor* residual = nullptr) {
   const int Nb = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int K = w.size(0), R = w.size(2), S = w.size(3);
   TORCH_CHECK(w.size(1) == C, "channel mismatch");
@@ -1597,6 +1690,12 @@ at::Tensor conv_fwd_igemm_t(at::Tensor x, at::Tensor w, long stride, long pad,
   auto out = at::empty({Nb, K, P, Q},
                        x.options().memory_format(at::MemoryFormat::ChannelsLast));
   auto stream = conv_stream();
+  if (residual != nullptr)
+    TORCH_CHECK(residual->sizes() == out.sizes() &&
+                residual->is_contiguous(at::MemoryFormat::ChannelsLast),
+                "conv_fwd_bn_igemm: residual must be a channels_last tensor "
+                "of the output's shape ", out.sizes(), ", got ",
+                residual->sizes());
 
   if (C == 3) {
     // stem fast path: pad x and w to 4 channels, tap-wise dwordx2 gathers
@@ -1620,12 +1719,13 @@ at::Tensor conv_fwd_igemm_t(at::Tensor x, at::Tensor w, long stride, long pad,
                Nb * P * Q, K, Kpad};
     const int bmt = pick_bmt(d, tile);
     const dim3 grid((d.N + BN - 1) / BN, (d.M + bmt - 1) / bmt);
-    auto* kern = bmt == 64 ? conv_igemm_kernel<T, 0, false, 64, true>
-                           : conv_igemm_kernel<T, 0, false, 128, true>;
+    auto* kern = bmt == 64
+        ? conv_igemm_kernel<T, 0, false, 64, true, BN, false, BNEPI>
+        : conv_igemm_kernel<T, 0, false, 128, true, BN, false, BNEPI>;
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream,
                        ptr16<T>(x4),
                        ptr16<T>(w4),
-                       reinterpret_cast<T*>(out.data_ptr()), d);
+                       reinterpret_cast<T*>(out.data_ptr()), d, ep);
     return out;
   }
 
@@ -1635,28 +1735,86 @@ at::Tensor conv_fwd_igemm_t(at::Tensor x, at::Tensor w, long stride, long pad,
   if (tile == 228 && fast && d.N >= 96) {
     const int nz = igemm_splits(d, splits);
     if (nz > 1) {
-      igemm_splitk_launch<T, 0>(x, w, out, d, nz);
+      igemm_splitk_launch<T, 0, BNEPI>(x, w, out, d, nz, ep);
       return out;
     }
     // 128x128 tile: halves the N-tile count and with it the A re-reads
     const dim3 grid((d.N + 127) / 128, (d.M + 127) / 128);
-    hipLaunchKernelGGL((conv_igemm_kernel<T, 0, true, 128, false, 128>), grid,
-                       dim3(256), 0, stream, ptr16<T>(x), ptr16<T>(w),
-                       reinterpret_cast<T*>(out.data_ptr()), d);
+    hipLaunchKernelGGL(
+        (conv_igemm_kernel<T, 0, true, 128, false, 128, false, BNEPI>), grid,
+        dim3(256), 0, stream, ptr16<T>(x), ptr16<T>(w),
+        reinterpret_cast<T*>(out.data_ptr()), d, ep);
     return out;
   }
   const int bmt = pick_bmt(d, tile);
   const dim3 grid((d.N + BN - 1) / BN, (d.M + bmt - 1) / bmt);
   auto* kern = bmt == 64
-      ? (fast ? conv_igemm_kernel<T, 0, true, 64>
-              : conv_igemm_kernel<T, 0, false, 64>)
-      : (fast ? conv_igemm_kernel<T, 0, true> : conv_igemm_kernel<T, 0, false>);
+      ? (fast ? conv_igemm_kernel<T, 0, true, 64, false, BN, false, BNEPI>
+              : conv_igemm_kernel<T, 0, false, 64, false, BN, false, BNEPI>)
+      : (fast ? conv_igemm_kernel<T, 0, true, BM, false, BN, false, BNEPI>
+              : conv_igemm_kernel<T, 0, false, BM, false, BN, false, BNEPI>);
   hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream,
                      ptr16<T>(x), ptr16<T>(w),
-                     reinterpret_cast<T*>(out.data_ptr()), d);
+                     reinterpret_cast<T*>(out.data_ptr()), d, ep);
   return out;
 }
+
+template <typename T>
+at::Tensor conv_fwd_bn_igemm_t(const at::Tensor& x, const at::Tensor& w,
+                               const at::Tensor& scale_shift,
+                               const at::Tensor* residual, bool relu,
+                               long stride, long pad, long tile, long splits) {
+  const long K = w.size(0);
+  BnEpi<T> ep;
+  ep.scale = scale_shift.data_ptr<float>() + 2 * K;
+  ep.shift = ep.scale + K;
+  ep.res = residual != nullptr ? ptr16<T>(*residual) : nullptr;
+  ep.relu = relu ? 1 : 0;
+  return conv_fwd_igemm_t<T, true>(x, w, stride, pad, tile, splits, ep,
+                                   residual);
+}
 }  // namespace
+
+// conv_fwd_igemm with the evaluation-mode BatchNorm folded into the epilogue:
+//   out = round(relu(conv(x, w) * scale[k] + shift[k] + residual))
+// in one launch (tile 228 with splits > 1: the split-K launch and a reduce
+// that applies it). scale_shift is the fp32 [4][K] table bn_fwd_apply reads:
+// rows 2 and 3 are scale and shift. residual, if given, has the output's
+// shape, dtype and channels_last layout. Inference only.
+at::Tensor conv_fwd_bn_igemm(at::Tensor x, at::Tensor w,
+                             at::Tensor scale_shift,
+                             c10::optional<at::Tensor> residual, bool relu,
+                             long stride, long pad, long tile, long splits) {
+  check_nhwc_16(x, "x"); check_nhwc_16(w, "w");
+  check_same_16(x, "x", w, "w");
+  TORCH_CHECK(scale_shift.is_cuda() && scale_shift.is_contiguous() &&
+              scale_shift.scalar_type() == at::kFloat &&
+              scale_shift.dim() == 2 && scale_shift.size(0) == 4 &&
+              scale_shift.size(1) == w.size(0),
+              "conv_fwd_bn_igemm: scale_shift must be a contiguous fp32 [4][",
+              w.size(0), "] HIP tensor (rows 2, 3 = scale, shift), got ",
+              scale_shift.scalar_type(), " ", scale_shift.sizes());
+  const bool has_res = residual.has_value() && residual->defined();
+  if (has_res) {
+    TORCH_CHECK(residual->is_cuda() && residual->dim() == 4,
+                "conv_fwd_bn_igemm: residual must be a 4-D HIP tensor");
+    check_same_16(x, "x", *residual, "residual");
+  }
+  // the split-K reduce reads its 8 channels as 16-byte vectors when K % 8 == 0
+  if (w.size(0) % 8 == 0) {
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(scale_shift.data_ptr()) & 15) == 0
+                && (!has_res || (reinterpret_cast<uintptr_t>(
+                                     residual->data_ptr()) & 15) == 0),
+                "conv_fwd_bn_igemm: scale_shift and residual must be 16-byte "
+                "aligned");
+  }
+  const at::Tensor* res = has_res ? &*residual : nullptr;
+  return x.scalar_type() == at::kHalf
+      ? conv_fwd_bn_igemm_t<_Float16>(x, w, scale_shift, res, relu, stride,
+                                      pad, tile, splits)
+      : conv_fwd_bn_igemm_t<__bf16>(x, w, scale_shift, res, relu, stride, pad,
+                                    tile, splits);
+}
 
 // out (N,K,P,Q) channels_last <- x (N,C,H,W) channels_last, w (K,C,R,S)
 // channels_last (memory [K][R][S][C]); bf16 or fp16, out in the same dtype.
@@ -1707,7 +1865,7 @@ at::Tensor conv_dgrad_igemm_t(at::Tensor dy, at::Tensor wT, long H, long W,
                            : conv_igemm_kernel<T, 2, true, 128>;
     hipLaunchKernelGGL(kern, grid, dim3(256), 0,
                        conv_stream(), ptr16<T>(dy), ptr16<T>(wT),
-                       reinterpret_cast<T*>(dx.data_ptr()), d2);
+                       reinterpret_cast<T*>(dx.data_ptr()), d2, NoEpi{});
     return dx;
   }
   if (tile == 228 && fast && d.N >= 96) {
@@ -1719,7 +1877,7 @@ at::Tensor conv_dgrad_igemm_t(at::Tensor dy, at::Tensor wT, long H, long W,
     const dim3 grid((d.N + 127) / 128, (d.M + 127) / 128);
     hipLaunchKernelGGL((conv_igemm_kernel<T, 1, true, 128, false, 128>), grid,
                        dim3(256), 0, conv_stream(), ptr16<T>(dy), ptr16<T>(wT),
-                       reinterpret_cast<T*>(dx.data_ptr()), d);
+                       reinterpret_cast<T*>(dx.data_ptr()), d, NoEpi{});
     return dx;
   }
   const int bmt = pick_bmt(d, tile);
@@ -1730,7 +1888,7 @@ at::Tensor conv_dgrad_igemm_t(at::Tensor dy, at::Tensor wT, long H, long W,
       : (fast ? conv_igemm_kernel<T, 1, true> : conv_igemm_kernel<T, 1, false>);
   hipLaunchKernelGGL(kern, grid, dim3(256), 0, conv_stream(),
                      ptr16<T>(dy), ptr16<T>(wT),
-                     reinterpret_cast<T*>(dx.data_ptr()), d);
+                     reinterpret_cast<T*>(dx.data_ptr()), d, NoEpi{});
   return dx;
 }
 }  // namespace

@@ -2669,6 +2669,10 @@ at::Tensor class_rank(at::Tensor logits, at::Tensor target) {
 at::Tensor conv_build_wT(at::Tensor w);
 at::Tensor conv_fwd_igemm(at::Tensor x, at::Tensor w, long stride, long pad,
                           long tile, long splits);
+at::Tensor conv_fwd_bn_igemm(at::Tensor x, at::Tensor w,
+                             at::Tensor scale_shift,
+                             c10::optional<at::Tensor> residual, bool relu,
+                             long stride, long pad, long tile, long splits);
 at::Tensor conv_dgrad_igemm(at::Tensor dy, at::Tensor wT, long H, long W,
                             long stride, long pad, long tile, long splits);
 at::Tensor conv_wgrad_igemm(at::Tensor dy, at::Tensor x, long R, long S,
@@ -2698,6 +2702,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "slices + one reduce",
         py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad"),
         py::arg("tile") = 0, py::arg("splits") = 1);
+  m.def("conv_fwd_bn_igemm", &conv_fwd_bn_igemm,
+        "conv_fwd_igemm with eval-mode BatchNorm (+residual)(+relu) applied "
+        "to the fp32 accumulator: scale_shift is fp32 [4][K], rows 2, 3 = "
+        "scale, shift; tile and splits as in conv_fwd_igemm",
+        py::arg("x"), py::arg("w"), py::arg("scale_shift"),
+        py::arg("residual") = py::none(), py::arg("relu") = false,
+        py::arg("stride") = 1, py::arg("pad") = 0, py::arg("tile") = 0,
+        py::arg("splits") = 1);
   m.def("conv_dgrad_igemm", &conv_dgrad_igemm,
         "implicit-GEMM conv input-grad (NHWC bf16|fp16, MFMA); "
         "tile 0=auto|64|128|228 (128x128); splits > 1 with tile 228: split-K "

@@ -87,6 +87,9 @@ class TrainConfig:
     # exponential moving average of the weights and BatchNorm statistics,
     # kept by the fused step and used for evaluation (core/ema.py); 0 = off
     ema_decay: float = 0.0
+    # evaluation forward with BatchNorm, the residual add and ReLU folded
+    # into the conv kernels' epilogue (core/inference.py); training is the same
+    fused_eval: bool = False
 
     # native kernels
     native_ops: bool = True           # HIP kernels when extension present; fail loudly on GPU if absent
@@ -209,6 +212,10 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                    help="decay of the weight average kept by the fused SGD "
                         "step, in [0, 1); evaluation and the best checkpoint "
                         "then use the averaged weights; 0 = off")
+    p.add_argument("--fused_eval", "--fused-eval", dest="fused_eval",
+                   action="store_true",
+                   help="evaluate with BatchNorm, add and ReLU fused into the "
+                        "conv kernels (one launch per layer)")
     return p
 
 
@@ -252,6 +259,8 @@ def config_from_args(args: argparse.Namespace, **overrides) -> TrainConfig:
         kw["hflip"] = True
     if getattr(args, "lars", False):
         kw["lars"] = True
+    if getattr(args, "fused_eval", False):
+        kw["fused_eval"] = True
     for name in ("label_smoothing", "cutmix_alpha", "cutmix_prob",
                  "lars_eta", "clip_grad_norm", "ema_decay"):
         if getattr(args, name, None) is not None:

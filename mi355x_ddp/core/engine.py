@@ -11,6 +11,7 @@ is one implementation with the reference's latent bugs fixed:
 """
 from __future__ import annotations
 
+import contextlib
 import time
 from typing import Optional
 
@@ -21,6 +22,7 @@ from ..ops.batchnorm import (defer_num_batches_tracked,
                              flush_num_batches_tracked)
 from . import dist as dist_utils
 from .amp import DynamicLossScaler, autocast_ctx
+from .inference import fused_inference
 from .metrics import AverageMeter, JsonlSink, ProgressMeter, accuracy
 from .watchdog import StepWatchdog
 
@@ -166,28 +168,33 @@ def validate(model, loader, criterion, device, cfg: TrainConfig,
     progress = ProgressMeter(len(loader), [batch_time, losses, top1, top5],
                              prefix="Test: ")
     end = time.time()
-    for i, (images, labels) in enumerate(loader):
-        if cfg.max_eval_steps is not None and i >= cfg.max_eval_steps:
-            break
-        images = images.to(device, non_blocking=True)
-        labels = labels.to(device, non_blocking=True)
-        if cfg.channels_last:
-            images = images.to(memory_format=torch.channels_last)
-        with autocast_ctx(cfg.amp, device.type):
-            outputs = model(images)
-            loss = criterion(outputs, labels)
-        acc1, acc5 = accuracy(outputs.float(), labels, topk=(1, 5))
-        dist_utils.barrier()
-        reduced_loss = dist_utils.reduce_mean(loss.detach().float(), nprocs)
-        reduced_acc1 = dist_utils.reduce_mean(acc1, nprocs)
-        reduced_acc5 = dist_utils.reduce_mean(acc5, nprocs)
-        losses.update(float(reduced_loss), images.size(0))
-        top1.update(float(reduced_acc1), images.size(0))
-        top5.update(float(reduced_acc5), images.size(0))
-        batch_time.update(time.time() - end)
-        end = time.time()
-        if i % cfg.log_interval == 0 and dist_utils.is_main_process():
-            progress.display(i)
+    # cfg.fused_eval: conv + BN (+ add) (+ ReLU) as one kernel per layer, folded
+    # from the weights the model holds now (inside an EMA swap: the averages)
+    fused = fused_inference(model) if getattr(cfg, "fused_eval", False) \
+        else contextlib.nullcontext()
+    with fused:
+        for i, (images, labels) in enumerate(loader):
+            if cfg.max_eval_steps is not None and i >= cfg.max_eval_steps:
+                break
+            images = images.to(device, non_blocking=True)
+            labels = labels.to(device, non_blocking=True)
+            if cfg.channels_last:
+                images = images.to(memory_format=torch.channels_last)
+            with autocast_ctx(cfg.amp, device.type):
+                outputs = model(images)
+                loss = criterion(outputs, labels)
+            acc1, acc5 = accuracy(outputs.float(), labels, topk=(1, 5))
+            dist_utils.barrier()
+            reduced_loss = dist_utils.reduce_mean(loss.detach().float(), nprocs)
+            reduced_acc1 = dist_utils.reduce_mean(acc1, nprocs)
+            reduced_acc5 = dist_utils.reduce_mean(acc5, nprocs)
+            losses.update(float(reduced_loss), images.size(0))
+            top1.update(float(reduced_acc1), images.size(0))
+            top5.update(float(reduced_acc5), images.size(0))
+            batch_time.update(time.time() - end)
+            end = time.time()
+            if i % cfg.log_interval == 0 and dist_utils.is_main_process():
+                progress.display(i)
     if dist_utils.is_main_process():
         print(f" * Acc@1 {top1.avg:.3f} Acc@5 {top5.avg:.3f}", flush=True)
         if sink is not None:

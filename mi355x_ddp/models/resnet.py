@@ -16,7 +16,39 @@ import torch
 import torch.nn as nn
 
 from ..ops import bn_relu, bn_add_relu
+from ..ops.fused_eval import FOLDED_ATTR, conv_bn_act
 from ..ops.pool import GlobalAvgPool2d
+
+
+def conv_bn(x, conv, bn, relu: bool = True, identity=None):
+    """`bn_relu(conv(x), bn, relu)`, or `bn_add_relu(conv(x), identity, bn)`
+    when `identity` is given: every conv + BatchNorm pair of the zoo. That is
+    exactly what runs, in that order, unless `bn` carries folded tables
+    (core/inference.py) and is not training; then the pair is one
+    `conv_bn_act`. `identity` may be a function without arguments, called
+    where the join needs its value: after the conv on the plain path, as the
+    blocks always ordered it, and before the fused call that consumes it."""
+    if not bn.training:
+        # the tables are a plain instance attribute; looking in __dict__
+        # spares a training or unfolded forward nn.Module's __getattr__
+        folded = bn.__dict__.get(FOLDED_ATTR)
+        if folded is not None:
+            if callable(identity):
+                identity = identity()
+            return conv_bn_act(x, conv, folded, relu, identity, bn=bn)
+    out = conv(x)
+    if identity is None:
+        return bn_relu(out, bn, relu)
+    if callable(identity):
+        identity = identity()
+    return bn_add_relu(out, identity, bn)
+
+
+def _identity(block, x):
+    """The residual branch of a block: x, or its 1x1 projection."""
+    if block.downsample is None:
+        return x
+    return conv_bn(x, block.downsample[0], block.downsample[1], relu=False)
 
 
 def _conv3x3(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
@@ -46,12 +78,9 @@ class BasicBlock(nn.Module):
             )
 
     def forward(self, x):
-        identity = x
-        out = bn_relu(self.conv1(x), self.bn1)
-        out = self.conv2(out)
-        if self.downsample is not None:
-            identity = bn_relu(self.downsample[0](x), self.downsample[1], relu=False)
-        return bn_add_relu(out, identity, self.bn2)
+        out = conv_bn(x, self.conv1, self.bn1)
+        return conv_bn(out, self.conv2, self.bn2,
+                       identity=lambda: _identity(self, x))
 
 
 class Bottleneck(nn.Module):
@@ -76,13 +105,10 @@ class Bottleneck(nn.Module):
             )
 
     def forward(self, x):
-        identity = x
-        out = bn_relu(self.conv1(x), self.bn1)
-        out = bn_relu(self.conv2(out), self.bn2)
-        out = self.conv3(out)
-        if self.downsample is not None:
-            identity = bn_relu(self.downsample[0](x), self.downsample[1], relu=False)
-        return bn_add_relu(out, identity, self.bn3)
+        out = conv_bn(x, self.conv1, self.bn1)
+        out = conv_bn(out, self.conv2, self.bn2)
+        return conv_bn(out, self.conv3, self.bn3,
+                       identity=lambda: _identity(self, x))
 
 
 class ResNet(nn.Module):
@@ -119,7 +145,7 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        out = bn_relu(self.conv1(x), self.bn1)
+        out = conv_bn(x, self.conv1, self.bn1)
         if self.maxpool is not None:
             out = self.maxpool(out)
         out = self.layer1(out)
@@ -129,6 +155,20 @@ class ResNet(nn.Module):
         out = self.avgpool(out)
         out = torch.flatten(out, 1)
         return self.fc(out)
+
+
+def conv_bn_pairs(model: nn.Module):
+    """Every (conv, BatchNorm) pair that `conv_bn` runs in `model`, in module
+    order: what core/inference.py folds."""
+    for m in model.modules():
+        if isinstance(m, (ResNet, BasicBlock, Bottleneck)):
+            for i in (1, 2, 3):
+                conv = getattr(m, f"conv{i}", None)
+                if conv is not None:
+                    yield conv, getattr(m, f"bn{i}")
+        if isinstance(m, (BasicBlock, Bottleneck)) and \
+                m.downsample is not None:
+            yield m.downsample[0], m.downsample[1]
 
 
 def resnet18(num_classes: int = 100) -> ResNet:

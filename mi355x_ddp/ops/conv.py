@@ -242,8 +242,18 @@ def tune_report() -> str:
     for key in sorted(_TUNE_CACHE, key=str):
         choice = _TUNE_CACHE[key]
         # wgrad choices are (wtile, splits) pairs too, printed as they are
-        label = _choice_label(choice) if key[0] in ("fwd", "dgrad") \
-            else ("MIOpen" if choice == MIOPEN else str(choice))
+        if key[0] == "fwd_bn":   # ops/fused_eval.py: conv + eval BN
+            if choice == UNFUSED:
+                label = "unfused: conv2d, then bn_fwd_apply"
+            elif choice == TILE_128X128:
+                label = "fused BN epilogue, 128x128 tile"
+            elif isinstance(choice, tuple):
+                label = f"fused BN epilogue, {_choice_label(choice)}"
+            else:
+                label = f"fused BN epilogue, tile {choice}"
+        else:
+            label = _choice_label(choice) if key[0] in ("fwd", "dgrad") \
+                else ("MIOpen" if choice == MIOPEN else str(choice))
         # _ConvIGEMM's keys carry the dtype of the pass's operands at [1]
         if len(key) > 1 and isinstance(key[1], torch.dtype):
             dt, rest = str(key[1]).replace("torch.", ""), key[2:]
@@ -254,6 +264,7 @@ def tune_report() -> str:
 
 
 MIOPEN = -1  # tuner sentinel: this pass is fastest on the MIOpen kernel
+UNFUSED = -2  # "fwd_bn" sentinel: the plain conv2d, then bn_fwd_apply
 
 
 # --------------------------------------------------------------------------
@@ -524,6 +535,30 @@ class MI355Conv2d(nn.Conv2d):
             weight = weight.to(dt)
         return conv2d(x, weight, self.stride, self.padding, self.dilation,
                       self.groups)
+
+    def native_operands(self, x: torch.Tensor
+                        ) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """(input, filter) as `forward` would hand them to the forward igemm
+        kernel, or None where `forward` would not run that kernel for `x`
+        (torch's conv instead). The filter is the WeightShadow's `w16` where
+        `forward` would use the shadow, so a changed weight is picked up by
+        the same stamp. For callers that replace the forward kernel by a
+        sibling of it (ops/fused_eval.py)."""
+        weight = self.weight
+        dt = torch.get_autocast_dtype("cuda") \
+            if torch.is_autocast_enabled() and x.is_cuda else None
+        if dt == torch.float16 and not native_conv_fp16_wanted():
+            dt = None
+        if dt in _NATIVE_DTYPES:
+            x = x.to(dt)
+            if self._shadow_ok(x, weight):
+                return x, _shadow_for(weight, dt).w16
+            weight = weight.to(dt)
+        if not _native_ok(x, weight, self.stride, self.padding, self.dilation,
+                          self.groups):
+            return None
+        return (x.contiguous(memory_format=torch.channels_last),
+                weight.detach().contiguous(memory_format=torch.channels_last))
 
     def _shadow_ok(self, x: torch.Tensor, weight: torch.Tensor) -> bool:
         return (weight_shadows_wanted() and
