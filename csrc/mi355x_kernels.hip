@@ -2682,6 +2682,15 @@ void multi_tensor_build_wT(std::vector<at::Tensor> w16s,
                            std::vector<at::Tensor> wTs);
 void conv_prep_weight(at::Tensor w32, at::Tensor w16, at::Tensor wT);
 
+// csrc/conv_grouped.hip — grouped 3x3 convolution on packed MFMA operands
+std::tuple<at::Tensor, at::Tensor> conv_grouped_prep(at::Tensor w,
+                                                     long groups);
+at::Tensor conv_grouped_fwd(at::Tensor x, at::Tensor wp, long stride);
+at::Tensor conv_grouped_dgrad(at::Tensor dy, at::Tensor wpT, long H, long W,
+                              long stride);
+at::Tensor conv_grouped_wgrad(at::Tensor dy, at::Tensor x, long groups,
+                              long stride, long splits);
+
 // csrc/data_aug.hip — device-resident input pipeline (crop/flip/normalize)
 std::tuple<at::Tensor, at::Tensor> batch_augment(
     at::Tensor images_u8, at::Tensor labels_i64, at::Tensor idx_i32,
@@ -2731,6 +2740,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_prep_weight", &conv_prep_weight,
         "w16 <- w32 rounded to w16.dtype (bf16|fp16) and wT <- "
         "rotated/transposed w16, one launch");
+  m.def("conv_grouped_prep", &conv_grouped_prep,
+        "(C, Cg, 3, 3) bf16|fp16 filter -> (wp, wpT): the block-diagonal "
+        "[C/P][9][P][P] forward and input-grad operands, P = max(Cg, 32)",
+        py::arg("w"), py::arg("groups"));
+  m.def("conv_grouped_fwd", &conv_grouped_fwd,
+        "grouped 3x3 pad-1 conv forward (NHWC bf16|fp16, MFMA), stride 1|2",
+        py::arg("x"), py::arg("wp"), py::arg("stride") = 1);
+  m.def("conv_grouped_dgrad", &conv_grouped_dgrad,
+        "grouped 3x3 pad-1 conv input-grad on the rotated operand wpT",
+        py::arg("dy"), py::arg("wpT"), py::arg("H"), py::arg("W"),
+        py::arg("stride") = 1);
+  m.def("conv_grouped_wgrad", &conv_grouped_wgrad,
+        "grouped 3x3 pad-1 conv weight-grad -> channels_last (C, Cg, 3, 3) in "
+        "the input dtype; two-stage, no atomics; splits 0=auto",
+        py::arg("dy"), py::arg("x"), py::arg("groups"),
+        py::arg("stride") = 1, py::arg("splits") = 0);
   m.def("bn_stats", &bn_stats, "per-channel sum/sqsum (NCHW)");
   m.def("bn_stats_packed", &bn_stats_packed,
         "per-channel {sum,sqsum} packed [2C], no-atomic NHWC v2");

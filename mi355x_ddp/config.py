@@ -21,7 +21,8 @@ CIFAR100_STD = (0.2673342858792401, 0.2564384629170883, 0.27615047132568404)
 @dataclass
 class TrainConfig:
     # model / task
-    arch: str = "resnet18"            # resnet18 | resnet34 | resnet50
+    arch: str = "resnet18"            # resnet18 | resnet34 | resnet50 |
+    #   resnext50_32x4d | resnext101_32x8d | resnext50_32x4d_imagenet
     num_classes: int = 100
     image_size: int = 32
 
@@ -152,7 +153,8 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--arch", default="resnet18", type=str,
                    choices=["resnet18", "resnet34", "resnet50", "resnet101",
                             "resnet152", "resnet18_imagenet",
-                            "resnet50_imagenet"])
+                            "resnet50_imagenet", "resnext50_32x4d",
+                            "resnext101_32x8d", "resnext50_32x4d_imagenet"])
     p.add_argument("--amp", default=None, type=str,
                    choices=[None, "fp32", "bf16", "fp16", "bf16_o2"],
                    help="precision. fp32: convs on MIOpen. bf16: autocast, "

@@ -1,2 +1,4 @@
 from .resnet import (ResNet, BasicBlock, Bottleneck, resnet18, resnet34,
-                     resnet50, resnet101, resnet152, build_model)  # noqa: F401
+                     resnet50, resnet101, resnet152, resnext50_32x4d,
+                     resnext101_32x8d, resnext50_32x4d_imagenet,
+                     build_model)  # noqa: F401

@@ -51,8 +51,10 @@ def _identity(block, x):
     return conv_bn(x, block.downsample[0], block.downsample[1], relu=False)
 
 
-def _conv3x3(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
-    return nn.Conv2d(cin, cout, kernel_size=3, stride=stride, padding=1, bias=False)
+def _conv3x3(cin: int, cout: int, stride: int = 1,
+             groups: int = 1) -> nn.Conv2d:
+    return nn.Conv2d(cin, cout, kernel_size=3, stride=stride, padding=1,
+                     groups=groups, bias=False)
 
 
 def _conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
@@ -85,17 +87,21 @@ class BasicBlock(nn.Module):
 
 class Bottleneck(nn.Module):
     """1x1 -> 3x3 -> 1x1; expansion 4 (reference utils/model.py:32-59, minus
-    its stray debug print at :37)."""
+    its stray debug print at :37). `groups` and `base_width` make it the
+    ResNeXt block: the inner width is int(cout * base_width / 64) * groups and
+    the 3x3 is grouped; the defaults give the plain block."""
 
     expansion = 4
 
-    def __init__(self, cin: int, cout: int, stride: int = 1):
+    def __init__(self, cin: int, cout: int, stride: int = 1,
+                 groups: int = 1, base_width: int = 64):
         super().__init__()
-        self.conv1 = _conv1x1(cin, cout)
-        self.bn1 = nn.BatchNorm2d(cout)
-        self.conv2 = _conv3x3(cout, cout, stride)
-        self.bn2 = nn.BatchNorm2d(cout)
-        self.conv3 = _conv1x1(cout, cout * self.expansion)
+        width = int(cout * base_width / 64) * groups
+        self.conv1 = _conv1x1(cin, width)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.conv2 = _conv3x3(width, width, stride, groups)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.conv3 = _conv1x1(width, cout * self.expansion)
         self.bn3 = nn.BatchNorm2d(cout * self.expansion)
         self.downsample = None
         if stride != 1 or cin != cout * self.expansion:
@@ -113,9 +119,13 @@ class Bottleneck(nn.Module):
 
 class ResNet(nn.Module):
     def __init__(self, block, num_blocks, num_classes: int = 100,
-                 imagenet_stem: bool = False):
+                 imagenet_stem: bool = False, groups: int = 1,
+                 base_width: int = 64):
         super().__init__()
         self.in_channels = 64
+        # ResNeXt (Bottleneck only): passed to every block when not default
+        self.block_kwargs = {} if (groups, base_width) == (1, 64) else \
+            {"groups": groups, "base_width": base_width}
         if imagenet_stem:
             # standard ImageNet stem: 7x7 s2 + 3x3 s2 maxpool (4x spatial
             # reduction before stage 1) — beyond the reference zoo, for
@@ -140,7 +150,8 @@ class ResNet(nn.Module):
         strides = [stride] + [1] * (blocks - 1)
         layers = []
         for s in strides:
-            layers.append(block(self.in_channels, cout, s))
+            layers.append(block(self.in_channels, cout, s,
+                                **self.block_kwargs))
             self.in_channels = cout * block.expansion
         return nn.Sequential(*layers)
 
@@ -205,13 +216,38 @@ def resnet18_imagenet(num_classes: int = 100) -> ResNet:
     return ResNet(BasicBlock, [2, 2, 2, 2], num_classes, imagenet_stem=True)
 
 
+def resnext50_32x4d(num_classes: int = 100) -> ResNet:
+    """ResNeXt-50 32x4d on the CIFAR stem: the Bottleneck zoo with a grouped
+    3x3 (32 groups of 4, 8, 16, 32 channels over the four stages), which runs
+    on the packed grouped kernels (ops/conv.py)."""
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, groups=32,
+                  base_width=4)
+
+
+def resnext101_32x8d(num_classes: int = 100) -> ResNet:
+    return ResNet(Bottleneck, [3, 4, 23, 3], num_classes, groups=32,
+                  base_width=8)
+
+
+def resnext50_32x4d_imagenet(num_classes: int = 100) -> ResNet:
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, imagenet_stem=True,
+                  groups=32, base_width=4)
+
+
 _FACTORIES = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50,
               "resnet101": resnet101, "resnet152": resnet152,
               "resnet18_imagenet": resnet18_imagenet,
               "resnet50_imagenet": resnet50_imagenet}
 
 
+# kept apart from _FACTORIES, whose key set is the plain ResNet zoo
+_RESNEXT_FACTORIES = {"resnext50_32x4d": resnext50_32x4d,
+                      "resnext101_32x8d": resnext101_32x8d,
+                      "resnext50_32x4d_imagenet": resnext50_32x4d_imagenet}
+
+
 def build_model(arch: str, num_classes: int = 100) -> ResNet:
-    if arch not in _FACTORIES:
-        raise ValueError(f"unknown arch {arch!r}; choose from {sorted(_FACTORIES)}")
-    return _FACTORIES[arch](num_classes)
+    factories = {**_FACTORIES, **_RESNEXT_FACTORIES}
+    if arch not in factories:
+        raise ValueError(f"unknown arch {arch!r}; choose from {sorted(factories)}")
+    return factories[arch](num_classes)

@@ -39,6 +39,13 @@ cast node in either direction and results are bit-equal to the cast path.
 ``MI355X_WEIGHT_SHADOWS=0`` restores the per-call casts (A/B switch);
 ``MI355X_CHECK_SHADOWS=1`` verifies the shadows against a fresh cast and
 rotate at every forward (tests only: it synchronises with the host).
+
+Grouped convolution. A 3x3 pad-1 grouped conv with 4 to 64 channels per group
+(every grouped layer of ResNeXt-50 32x4d and ResNeXt-101 32x8d) runs on the
+packed kernels of csrc/conv_grouped.hip through ``_ConvGrouped`` (see
+``_grouped_ok`` for the scope); ``MI355X_NATIVE_GROUPED=0`` sends grouped
+convs back to torch's conv. Such a weight has no shadow: it is cast per call
+and packed once per forward.
 """
 from __future__ import annotations
 
@@ -69,6 +76,10 @@ def autotune_wanted() -> bool:
 
 def conv_splitk_wanted() -> bool:
     return os.environ.get("MI355X_CONV_SPLITK", "1") == "1"
+
+
+def native_grouped_wanted() -> bool:
+    return os.environ.get("MI355X_NATIVE_GROUPED", "1") == "1"
 
 
 def weight_shadows_wanted() -> bool:
@@ -102,6 +113,52 @@ def _native_ok(x: torch.Tensor, weight: torch.Tensor, stride, padding,
         return False
     # square filters only (the ResNet zoo is 3x3 / 1x1)
     return weight.shape[2] == weight.shape[3]
+
+
+_GROUPED_WIDTHS = (4, 8, 16, 32, 64)   # channels per group the kernels take
+
+
+def _grouped_ok(x: torch.Tensor, weight: torch.Tensor, stride, padding,
+                dilation, groups) -> bool:
+    """The grouped kernels (csrc/conv_grouped.hip) take this conv: 3x3, pad 1,
+    dilation 1, stride 1 or 2, channels_last, x and weight in one 16-bit
+    dtype, in_channels == out_channels == C, C / groups in {4, 8, 16, 32, 64}
+    and C a multiple of the pack width max(C / groups, 32)."""
+    if not native_grouped_wanted() or not native_conv_wanted() or \
+            not _backend.native_enabled(x):
+        return False
+    if x.dtype not in _NATIVE_DTYPES or weight.dtype != x.dtype:
+        return False
+    if x.dtype == torch.float16 and not native_conv_fp16_wanted():
+        return False
+    if groups == 1 or x.dim() != 4 or weight.dim() != 4:
+        return False
+    if tuple(weight.shape[2:]) != (3, 3) or tuple(padding) != (1, 1) or \
+            tuple(dilation) != (1, 1) or tuple(stride) not in ((1, 1), (2, 2)):
+        return False
+    C = x.shape[1]
+    if weight.shape[0] != C or C % groups != 0:
+        return False
+    cg = C // groups
+    if cg not in _GROUPED_WIDTHS or weight.shape[1] != cg or \
+            C % max(cg, 32) != 0:
+        return False
+    return x.is_contiguous(memory_format=torch.channels_last)
+
+
+class _Calls:
+    """Launch counters of the native grouped passes (one per call of the
+    extension function outside the tuner's measurements): lets tests and
+    users see that the native path ran."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self) -> None:
+        self.fwd = self.dgrad = self.wgrad = 0
+
+
+grouped_calls = _Calls()
 
 
 # --------------------------------------------------------------------------
@@ -251,6 +308,14 @@ def tune_report() -> str:
                 label = f"fused BN epilogue, {_choice_label(choice)}"
             else:
                 label = f"fused BN epilogue, tile {choice}"
+        elif key[0] in ("g_fwd", "g_dgrad", "g_wgrad"):   # _ConvGrouped
+            if choice == MIOPEN:
+                label = "MIOpen"
+            elif isinstance(choice, tuple):
+                label = "native grouped, splits " + \
+                    ("auto" if choice[1] == 0 else str(choice[1]))
+            else:
+                label = "native grouped"
         else:
             label = _choice_label(choice) if key[0] in ("fwd", "dgrad") \
                 else ("MIOpen" if choice == MIOPEN else str(choice))
@@ -498,10 +563,97 @@ class _ConvIGEMM(torch.autograd.Function):
         return dx, dw, None, None, None, None
 
 
+_GROUPED_WGRAD_SPLITS = (0, 1, 32)
+
+
+class _ConvGrouped(torch.autograd.Function):
+    """Grouped 3x3 pad-1 convolution on the packed kernels of
+    csrc/conv_grouped.hip: forward = conv_grouped_prep + conv_grouped_fwd,
+    backward = conv_grouped_dgrad and conv_grouped_wgrad as needed. Each pass
+    is the tuner's choice between the native kernel (default and first
+    candidate) and MIOpen, under the keys "g_fwd", "g_dgrad" and "g_wgrad".
+
+    `weight` is a 16-bit (C, C/groups, 3, 3) tensor: under autocast an fp32
+    parameter is cast per call and autograd's cast node carries the gradient
+    back to fp32. The packed operands are built once per forward, and the
+    input-grad form is kept on ctx for backward. Persistent packed shadows of
+    the weight, and their refresh in the FusedSGD step, are out of scope
+    here: a grouped weight gets no WeightShadow."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride: int, groups: int):
+        x = x.contiguous(memory_format=torch.channels_last)
+        C = _backend.C()
+        ctx.stride, ctx.groups = stride, groups
+        ctx.wpT = None
+        ctx.save_for_backward(x, weight)
+
+        def run(c):
+            if c == MIOPEN:
+                return F.conv2d(x, weight, None, stride, 1, 1, groups)
+            # packs on every call, the tuner's timed ones included: a native
+            # forward always pays for its prep launch
+            wp, ctx.wpT = C.conv_grouped_prep(weight, groups)
+            return C.conv_grouped_fwd(x, wp, stride)
+
+        key = _tune_key("g_fwd", x.dtype, x.shape, weight.shape, groups,
+                        stride)
+        choice = _tuned_choice(key, (0, MIOPEN), run, default=0)
+        if choice != MIOPEN:
+            grouped_calls.fwd += 1
+        return run(choice)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        stride, groups = ctx.stride, ctx.groups
+        C = _backend.C()
+        dx = dw = None
+
+        def miopen(mask):
+            return torch.ops.aten.convolution_backward(
+                dy, x, weight, None, [stride, stride], [1, 1], [1, 1], False,
+                [0, 0], groups, mask)
+
+        if ctx.needs_input_grad[0]:
+            def run_dx(c):
+                if c == MIOPEN:
+                    return miopen([True, False, False])[0]
+                if ctx.wpT is None:   # the forward ran on MIOpen
+                    ctx.wpT = C.conv_grouped_prep(weight, groups)[1]
+                return C.conv_grouped_dgrad(dy, ctx.wpT, x.shape[2],
+                                            x.shape[3], stride)
+
+            key = _tune_key("g_dgrad", x.dtype, dy.shape, x.shape, groups,
+                            stride)
+            choice = _tuned_choice(key, (0, MIOPEN), run_dx, default=0)
+            if choice != MIOPEN:
+                grouped_calls.dgrad += 1
+            dx = run_dx(choice)
+        if ctx.needs_input_grad[1]:
+            def run_dw(c):
+                if c == MIOPEN:
+                    return miopen([False, True, False])[1]
+                return C.conv_grouped_wgrad(dy, x, groups, stride, c[1])
+
+            key = _tune_key("g_wgrad", x.dtype, dy.shape, x.shape, groups,
+                            stride)
+            choice = _tuned_choice(
+                key, tuple(("splits", s) for s in _GROUPED_WGRAD_SPLITS) +
+                (MIOPEN,), run_dw, default=("splits", 0))
+            if choice != MIOPEN:
+                grouped_calls.wgrad += 1
+            dw = run_dw(choice)
+        return dx, dw, None, None
+
+
 def conv2d(x: torch.Tensor, weight: torch.Tensor, stride=(1, 1),
            padding=(0, 0), dilation=(1, 1), groups: int = 1) -> torch.Tensor:
     if _native_ok(x, weight, stride, padding, dilation, groups):
         return _ConvIGEMM.apply(x, weight, stride[0], padding[0])
+    if _grouped_ok(x, weight, stride, padding, dilation, groups):
+        return _ConvGrouped.apply(x, weight, stride[0], groups)
     return F.conv2d(x, weight, None, stride, padding, dilation, groups)
 
 

@@ -78,9 +78,78 @@ def collect_model_shapes(arch: str, image_size: int):
     return out
 
 
+# The grouped 3x3 layers of ResNeXt-50 32x4d on CIFAR input (32 groups), in
+# their stride-1 and stride-2 forms: (name, C, H = W of the input, stride)
+RESNEXT50_GROUPED_SHAPES = [
+    ("s1 128g32", 128, 32, 1),
+    ("s2 256g32/2", 256, 32, 2),
+    ("s2 256g32", 256, 16, 1),
+    ("s3 512g32/2", 512, 16, 2),
+    ("s3 512g32", 512, 8, 1),
+    ("s4 1024g32/2", 1024, 8, 2),
+    ("s4 1024g32", 1024, 4, 1),
+]
+
+
+def bench_grouped(args, dtype):
+    """Native grouped kernels against MIOpen, per pass. Each cell is the
+    median of `--windows` timeit windows, with the spread (max - min) / median
+    of the native windows; GB/s is the pass's compulsory traffic (x read and y
+    written once for fwd / dgrad, x and dy read once for wgrad) over the
+    native time."""
+    from mi355x_ddp import _C
+    N, groups = args.batch, 32
+    kw = dict(warmup=args.warmup, iters=args.iters)
+
+    def windows(fn):
+        ts = sorted(timeit(fn, **kw) for _ in range(args.windows))
+        return ts[len(ts) // 2], (ts[-1] - ts[0]) / ts[len(ts) // 2]
+
+    print(f"{'shape':>14} {'pass':>6} {'MIOpen us':>10} {'native us':>10} "
+          f"{'spread':>7} {'cfg':>10} {'x':>6} {'GB/s':>7}")
+    for name, c, h, stride in RESNEXT50_GROUPED_SHAPES:
+        x = torch.randn(N, c, h, h, device="cuda", dtype=dtype) \
+            .to(memory_format=torch.channels_last)
+        wt = (torch.randn(c, c // groups, 3, 3, device="cuda", dtype=dtype)
+              / (9 * c // groups) ** 0.5).to(memory_format=torch.channels_last)
+        y = F.conv2d(x, wt, None, stride, 1, 1, groups)
+        dy = torch.randn_like(y).to(memory_format=torch.channels_last)
+        wp, wpT = _C.conv_grouped_prep(wt, groups)
+        act_bytes = 2.0 * (x.numel() + y.numel())
+
+        def miopen_bwd(mask):
+            return torch.ops.aten.convolution_backward(
+                dy, x, wt, None, [stride, stride], [1, 1], [1, 1], False,
+                [0, 0], groups, mask)
+
+        def row(pss, tm, tn, spread, cfg):
+            print(f"{name:>14} {pss:>6} {tm:10.1f} {tn:10.1f} {spread:7.1%} "
+                  f"{cfg:>10} {tm/tn:6.2f} {act_bytes/tn/1e3:7.1f}",
+                  flush=True)
+
+        # the forward includes the per-call prep, as _ConvGrouped runs it
+        tm, _ = windows(lambda: F.conv2d(x, wt, None, stride, 1, 1, groups))
+        tn, sp = windows(lambda: _C.conv_grouped_fwd(
+            x, _C.conv_grouped_prep(wt, groups)[0], stride))
+        row("fwd", tm, tn, sp, "prep+fwd")
+        tm, _ = windows(lambda: miopen_bwd([True, False, False]))
+        tn, sp = windows(lambda: _C.conv_grouped_dgrad(dy, wpT, h, h, stride))
+        row("dgrad", tm, tn, sp, "")
+        tm, _ = windows(lambda: miopen_bwd([False, True, False]))
+        best = min((windows(lambda: _C.conv_grouped_wgrad(
+            dy, x, groups, stride, s)) + (f"splits {s}",) for s in (0, 1, 32)))
+        row("wgrad", tm, best[0], best[1], best[2])
+        del x, wt, y, dy, wp, wpT
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=256)
+    p.add_argument("--grouped", action="store_true",
+                   help="time the grouped 3x3 layers of ResNeXt-50 32x4d "
+                        "(native grouped kernels vs MIOpen) instead")
+    p.add_argument("--windows", type=int, default=5,
+                   help="timing windows per cell of the --grouped table")
     p.add_argument("--arch", type=str, default=None,
                    help="collect shapes from this model instead of the "
                         "static ResNet18 CIFAR table")
@@ -97,6 +166,8 @@ def main():
 
     dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
     print(f"# dtype {args.dtype}, batch {args.batch}")
+    if args.grouped:
+        return bench_grouped(args, dtype)
     N = args.batch
     if args.arch:
         rows = collect_model_shapes(args.arch, args.image_size)
