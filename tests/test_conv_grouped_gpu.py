@@ -6,6 +6,11 @@ fp32 conv ON THE CPU with `groups`, fed the same 16-bit-rounded operands;
 relative Frobenius error; 5e-4 for fp16 and 4e-3 for bf16, about 2.4x the
 reference's own rounding to the output format (2.04-2.12e-4 and 1.60-1.70e-3
 on all three passes of these shapes). Weights are randn / sqrt(9 * Cg).
+
+A norm over the whole tensor cannot see a few wrong elements. The elementwise
+check is tests/test_conv_grouped_exact_gpu.py: integer operands, `torch.equal`
+against the same CPU reference, on shapes that reach every kernel variant on
+more than one tile.
 """
 import functools
 
