@@ -2,8 +2,10 @@
 
 Covers every conv shape in the CIFAR ResNet18/50 zoo:
 3x3 s1, 3x3 s2, 1x1 s1, 1x1 s2 at C 64..512, plus the 3-channel stem
-(generic-gather path). Forward, input-grad and weight-grad each compared to
-an fp32 eager conv on the same data.
+(PADC: the padded-channel kernels). Forward, input-grad and weight-grad each
+compared to an fp32 eager conv on the same data by a relative norm over the
+whole tensor; the element-by-element check of every kernel variant, the
+generic gather path included, is tests/test_conv_exact_gpu.py.
 """
 import pytest
 import torch
@@ -15,7 +17,7 @@ DEV = "cuda"
 
 # (N, C, H, W, K, R, stride, pad)
 CONV_SHAPES = [
-    (8, 3, 32, 32, 64, 3, 1, 1),       # stem (generic path, C=3)
+    (8, 3, 32, 32, 64, 3, 1, 1),       # stem (PADC path, C=3)
     (8, 64, 32, 32, 64, 3, 1, 1),      # stage1 3x3
     (8, 64, 32, 32, 128, 3, 2, 1),     # stage2 downsampling 3x3 s2
     (8, 64, 32, 32, 128, 1, 2, 0),     # stage2 shortcut 1x1 s2
