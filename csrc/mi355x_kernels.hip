@@ -2691,6 +2691,13 @@ at::Tensor conv_grouped_dgrad(at::Tensor dy, at::Tensor wpT, long H, long W,
 at::Tensor conv_grouped_wgrad(at::Tensor dy, at::Tensor x, long groups,
                               long stride, long splits);
 
+// csrc/conv_depthwise.hip — depthwise 3x3 convolution, VALU from an LDS patch
+at::Tensor conv_dw_fwd(at::Tensor x, at::Tensor w, long stride);
+at::Tensor conv_dw_dgrad(at::Tensor dy, at::Tensor w, long H, long W,
+                         long stride);
+at::Tensor conv_dw_wgrad(at::Tensor dy, at::Tensor x, long stride,
+                         long splits);
+
 // csrc/data_aug.hip — device-resident input pipeline (crop/flip/normalize)
 std::tuple<at::Tensor, at::Tensor> batch_augment(
     at::Tensor images_u8, at::Tensor labels_i64, at::Tensor idx_i32,
@@ -2756,7 +2763,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "the input dtype; two-stage, no atomics; splits 0=auto",
         py::arg("dy"), py::arg("x"), py::arg("groups"),
         py::arg("stride") = 1, py::arg("splits") = 0);
-  m.def("bn_stats", &bn_stats, "per-channel sum/sqsum (NCHW)");
+  m.def("conv_dw_fwd", &conv_dw_fwd,
+        "depthwise 3x3 pad-1 conv forward (NHWC bf16|fp16, C % 8 == 0), "
+        "filter (C, 1, 3, 3) of any strides, stride 1|2",
+        py::arg("x"), py::arg("w"), py::arg("stride") = 1);
+  m.def("conv_dw_dgrad", &conv_dw_dgrad,
+        "depthwise 3x3 pad-1 conv input-grad of an H x W input, on the same "
+        "filter; dx is written in full",
+        py::arg("dy"), py::arg("w"), py::arg("H"), py::arg("W"),
+        py::arg("stride") = 1);
+  m.def("conv_dw_wgrad", &conv_dw_wgrad,
+        "depthwise 3x3 pad-1 conv weight-grad -> (C, 1, 3, 3) in the input "
+        "dtype; two-stage, no atomics; splits 0=auto",
+        py::arg("dy"), py::arg("x"), py::arg("stride") = 1,
+        py::arg("splits") = 0);
+  m.def("bn_stats",&bn_stats, "per-channel sum/sqsum (NCHW)");
   m.def("bn_stats_packed", &bn_stats_packed,
         "per-channel {sum,sqsum} packed [2C], no-atomic NHWC v2");
   m.def("bn_finalize", &bn_finalize,

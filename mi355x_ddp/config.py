@@ -22,7 +22,8 @@ CIFAR100_STD = (0.2673342858792401, 0.2564384629170883, 0.27615047132568404)
 class TrainConfig:
     # model / task
     arch: str = "resnet18"            # resnet18 | resnet34 | resnet50 |
-    #   resnext50_32x4d | resnext101_32x8d | resnext50_32x4d_imagenet
+    #   resnext50_32x4d | resnext101_32x8d | resnext50_32x4d_imagenet |
+    #   mobilenet_v1 | mobilenet_v1_imagenet
     num_classes: int = 100
     image_size: int = 32
 
@@ -154,7 +155,12 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                    choices=["resnet18", "resnet34", "resnet50", "resnet101",
                             "resnet152", "resnet18_imagenet",
                             "resnet50_imagenet", "resnext50_32x4d",
-                            "resnext101_32x8d", "resnext50_32x4d_imagenet"])
+                            "resnext101_32x8d", "resnext50_32x4d_imagenet",
+                            "mobilenet_v1", "mobilenet_v1_imagenet"],
+                   help="model: the CIFAR-stem ResNets and ResNeXts, their "
+                        "*_imagenet forms for 224 px inputs, or MobileNet-v1 "
+                        "(mobilenet_v1 for CIFAR, mobilenet_v1_imagenet with "
+                        "the stride-2 stem)")
     p.add_argument("--amp", default=None, type=str,
                    choices=[None, "fp32", "bf16", "fp16", "bf16_o2"],
                    help="precision. fp32: convs on MIOpen. bf16: autocast, "

@@ -171,8 +171,11 @@ class ResNet(nn.Module):
 def conv_bn_pairs(model: nn.Module):
     """Every (conv, BatchNorm) pair that `conv_bn` runs in `model`, in module
     order: what core/inference.py folds."""
+    # imported here: models/mobilenet.py builds on this module
+    from .mobilenet import DepthwiseSeparable, MobileNetV1
     for m in model.modules():
-        if isinstance(m, (ResNet, BasicBlock, Bottleneck)):
+        if isinstance(m, (ResNet, BasicBlock, Bottleneck, MobileNetV1,
+                          DepthwiseSeparable)):
             for i in (1, 2, 3):
                 conv = getattr(m, f"conv{i}", None)
                 if conv is not None:
@@ -246,8 +249,9 @@ _RESNEXT_FACTORIES = {"resnext50_32x4d": resnext50_32x4d,
                       "resnext50_32x4d_imagenet": resnext50_32x4d_imagenet}
 
 
-def build_model(arch: str, num_classes: int = 100) -> ResNet:
-    factories = {**_FACTORIES, **_RESNEXT_FACTORIES}
+def build_model(arch: str, num_classes: int = 100) -> nn.Module:
+    from .mobilenet import _MOBILENET_FACTORIES
+    factories = {**_FACTORIES, **_RESNEXT_FACTORIES, **_MOBILENET_FACTORIES}
     if arch not in factories:
         raise ValueError(f"unknown arch {arch!r}; choose from {sorted(factories)}")
     return factories[arch](num_classes)

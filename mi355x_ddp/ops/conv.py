@@ -46,6 +46,12 @@ packed kernels of csrc/conv_grouped.hip through ``_ConvGrouped`` (see
 ``_grouped_ok`` for the scope); ``MI355X_NATIVE_GROUPED=0`` sends grouped
 convs back to torch's conv. Such a weight has no shadow: it is cast per call
 and packed once per forward.
+
+Depthwise convolution. A 3x3 pad-1 conv with groups == in_channels ==
+out_channels (every depthwise layer of MobileNet-v1) runs on the kernels of
+csrc/conv_depthwise.hip through ``_ConvDepthwise`` (see ``_depthwise_ok`` for
+the scope); ``MI355X_NATIVE_DEPTHWISE=0`` sends it back to torch's conv. The
+kernels read the (C, 1, 3, 3) filter as it is: no shadow and no prep launch.
 """
 from __future__ import annotations
 
@@ -80,6 +86,10 @@ def conv_splitk_wanted() -> bool:
 
 def native_grouped_wanted() -> bool:
     return os.environ.get("MI355X_NATIVE_GROUPED", "1") == "1"
+
+
+def native_depthwise_wanted() -> bool:
+    return os.environ.get("MI355X_NATIVE_DEPTHWISE", "1") == "1"
 
 
 def weight_shadows_wanted() -> bool:
@@ -146,6 +156,31 @@ def _grouped_ok(x: torch.Tensor, weight: torch.Tensor, stride, padding,
     return x.is_contiguous(memory_format=torch.channels_last)
 
 
+def _depthwise_ok(x: torch.Tensor, weight: torch.Tensor, stride, padding,
+                  dilation, groups) -> bool:
+    """The depthwise kernels (csrc/conv_depthwise.hip) take this conv: 3x3,
+    pad 1, dilation 1, stride 1 or 2, channels_last, x and weight in one
+    16-bit dtype, groups == in_channels == out_channels == C (a (C, 1, 3, 3)
+    filter) and C a multiple of 8."""
+    if not native_depthwise_wanted() or not native_conv_wanted() or \
+            not _backend.native_enabled(x):
+        return False
+    if x.dtype not in _NATIVE_DTYPES or weight.dtype != x.dtype:
+        return False
+    if x.dtype == torch.float16 and not native_conv_fp16_wanted():
+        return False
+    if x.dim() != 4 or weight.dim() != 4:
+        return False
+    C = x.shape[1]
+    if groups != C or weight.shape[0] != C or weight.shape[1] != 1 or \
+            C % 8 != 0:
+        return False
+    if tuple(weight.shape[2:]) != (3, 3) or tuple(padding) != (1, 1) or \
+            tuple(dilation) != (1, 1) or tuple(stride) not in ((1, 1), (2, 2)):
+        return False
+    return x.is_contiguous(memory_format=torch.channels_last)
+
+
 class _Calls:
     """Launch counters of the native grouped passes (one per call of the
     extension function outside the tuner's measurements): lets tests and
@@ -159,6 +194,7 @@ class _Calls:
 
 
 grouped_calls = _Calls()
+depthwise_calls = _Calls()   # the same for the native depthwise passes
 
 
 # --------------------------------------------------------------------------
@@ -316,6 +352,14 @@ def tune_report() -> str:
                     ("auto" if choice[1] == 0 else str(choice[1]))
             else:
                 label = "native grouped"
+        elif key[0] in ("dw_fwd", "dw_dgrad", "dw_wgrad"):   # _ConvDepthwise
+            if choice == MIOPEN:
+                label = "MIOpen"
+            elif isinstance(choice, tuple):
+                label = "native depthwise, splits " + \
+                    ("auto" if choice[1] == 0 else str(choice[1]))
+            else:
+                label = "native depthwise"
         else:
             label = _choice_label(choice) if key[0] in ("fwd", "dgrad") \
                 else ("MIOpen" if choice == MIOPEN else str(choice))
@@ -648,12 +692,97 @@ class _ConvGrouped(torch.autograd.Function):
         return dx, dw, None, None
 
 
+_DEPTHWISE_WGRAD_SPLITS = (0, 8, 64)
+
+
+class _ConvDepthwise(torch.autograd.Function):
+    """Depthwise 3x3 pad-1 convolution on the kernels of
+    csrc/conv_depthwise.hip: conv_dw_fwd, and conv_dw_dgrad and conv_dw_wgrad
+    as backward needs them. Each pass is the tuner's choice between the native
+    kernel (default and first candidate) and MIOpen, under the keys "dw_fwd",
+    "dw_dgrad" and "dw_wgrad"; the last also ranges over a few split counts.
+
+    `weight` is a 16-bit (C, 1, 3, 3) tensor of any strides: the kernels read
+    it as it is, so there is no prep launch and nothing is kept for backward
+    but x and the weight. Under autocast an fp32 parameter is cast per call
+    and autograd's cast node carries the gradient back to fp32: a depthwise
+    weight gets no WeightShadow."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride: int):
+        x = x.contiguous(memory_format=torch.channels_last)
+        C = _backend.C()
+        ctx.stride = stride
+        ctx.save_for_backward(x, weight)
+        groups = x.shape[1]
+
+        def run(c):
+            if c == MIOPEN:
+                return F.conv2d(x, weight, None, stride, 1, 1, groups)
+            return C.conv_dw_fwd(x, weight, stride)
+
+        key = _tune_key("dw_fwd", x.dtype, x.shape, stride)
+        choice = _tuned_choice(key, (0, MIOPEN), run, default=0)
+        if choice != MIOPEN:
+            depthwise_calls.fwd += 1
+        return run(choice)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        stride, groups = ctx.stride, x.shape[1]
+        C = _backend.C()
+        dx = dw = None
+
+        def miopen(mask):
+            return torch.ops.aten.convolution_backward(
+                dy, x, weight, None, [stride, stride], [1, 1], [1, 1], False,
+                [0, 0], groups, mask)
+
+        if ctx.needs_input_grad[0]:
+            def run_dx(c):
+                if c == MIOPEN:
+                    return miopen([True, False, False])[0]
+                return C.conv_dw_dgrad(dy, weight, x.shape[2], x.shape[3],
+                                       stride)
+
+            key = _tune_key("dw_dgrad", x.dtype, dy.shape, x.shape, stride)
+            choice = _tuned_choice(key, (0, MIOPEN), run_dx, default=0)
+            if choice != MIOPEN:
+                depthwise_calls.dgrad += 1
+            dx = run_dx(choice)
+        if ctx.needs_input_grad[1]:
+            def run_dw(c):
+                if c == MIOPEN:
+                    return miopen([False, True, False])[1]
+                return C.conv_dw_wgrad(dy, x, stride, c[1])
+
+            key = _tune_key("dw_wgrad", x.dtype, dy.shape, x.shape, stride)
+            choice = _tuned_choice(
+                key, tuple(("splits", s) for s in _DEPTHWISE_WGRAD_SPLITS) +
+                (MIOPEN,), run_dw, default=("splits", 0))
+            if choice != MIOPEN:
+                depthwise_calls.wgrad += 1
+            dw = run_dw(choice)
+            # on (C, 1, 3, 3) the contiguous and the channels_last strides name
+            # one memory order; autograd's layout contract skips the size-1
+            # dim, the fused SGD step compares all four strides
+            if dw.stride() != weight.stride() and dw.is_contiguous() and (
+                    weight.is_contiguous() or weight.is_contiguous(
+                        memory_format=torch.channels_last)):
+                dw = dw.as_strided(weight.shape, weight.stride())
+        return dx, dw, None
+
+
 def conv2d(x: torch.Tensor, weight: torch.Tensor, stride=(1, 1),
            padding=(0, 0), dilation=(1, 1), groups: int = 1) -> torch.Tensor:
     if _native_ok(x, weight, stride, padding, dilation, groups):
         return _ConvIGEMM.apply(x, weight, stride[0], padding[0])
     if _grouped_ok(x, weight, stride, padding, dilation, groups):
         return _ConvGrouped.apply(x, weight, stride[0], groups)
+    if _depthwise_ok(x, weight, stride, padding, dilation, groups):
+        return _ConvDepthwise.apply(x, weight, stride[0])
     return F.conv2d(x, weight, None, stride, padding, dilation, groups)
 
 

@@ -142,9 +142,111 @@ def bench_grouped(args, dtype):
         del x, wt, y, dy, wp, wpT
 
 
+# The 13 depthwise layers of MobileNet-v1: (C, stride, multiplicity), in model
+# order; the input extent is --image-size (after the stem) divided by the
+# strides before the layer. --depthwise times every layer at both strides.
+MOBILENET_DW_LAYERS = [(32, 1, 1), (64, 2, 1), (128, 1, 1), (128, 2, 1),
+                       (256, 1, 1), (256, 2, 1), (512, 1, 5), (512, 2, 1),
+                       (1024, 1, 1)]
+
+
+def bench_depthwise(args, dtype):
+    """Native depthwise kernels against MIOpen, per pass, on the MobileNet-v1
+    depthwise shapes, each at stride 1 and 2 (`*` marks the stride the model
+    uses). The two sides alternate window by window; a cell is the median of
+    `--windows` windows and `spread` is (max - min) / median of the native
+    ones. GB/s is the compulsory traffic over the native time. Then the
+    mobilenet_v1 training step with MI355X_NATIVE_DEPTHWISE=1 against =0,
+    alternating in the same way."""
+    from mi355x_ddp import _C
+    N = args.batch
+    kw = dict(warmup=args.warmup, iters=args.iters)
+
+    def alternate(fa, fb):
+        ta, tb = [], []
+        for _ in range(args.windows):
+            ta.append(timeit(fa, **kw))
+            tb.append(timeit(fb, **kw))
+        ta.sort(), tb.sort()
+        m = len(ta) // 2
+        return ta[m], tb[m], (tb[-1] - tb[0]) / tb[m]
+
+    print(f"{'shape':>16} {'pass':>6} {'MIOpen us':>10} {'native us':>10} "
+          f"{'spread':>7} {'cfg':>10} {'x':>6} {'GB/s':>7}")
+    used, h = {}, args.image_size   # (C, extent) -> the strides the model has
+    for c, model_stride, _ in MOBILENET_DW_LAYERS:
+        used.setdefault((c, h), set()).add(model_stride)
+        h = (h - 1) // model_stride + 1
+    for (c, h), model_strides in used.items():
+        for stride in (1, 2):
+            mark = "*" if stride in model_strides else ""
+            name = f"{c}@{h}" + ("/2" if stride == 2 else "") + mark
+            x = torch.randn(N, c, h, h, device="cuda", dtype=dtype) \
+                .to(memory_format=torch.channels_last)
+            wt = (torch.randn(c, 1, 3, 3, device="cuda", dtype=dtype) / 3)
+            y = F.conv2d(x, wt, None, stride, 1, 1, c)
+            dy = torch.randn_like(y).to(memory_format=torch.channels_last)
+            act_bytes = 2.0 * (x.numel() + y.numel())
+
+            def miopen_bwd(mask):
+                return torch.ops.aten.convolution_backward(
+                    dy, x, wt, None, [stride, stride], [1, 1], [1, 1], False,
+                    [0, 0], c, mask)
+
+            def row(pss, tm, tn, spread, cfg=""):
+                print(f"{name:>16} {pss:>6} {tm:10.1f} {tn:10.1f} "
+                      f"{spread:7.1%} {cfg:>10} {tm/tn:6.2f} "
+                      f"{act_bytes/tn/1e3:7.1f}", flush=True)
+
+            row("fwd", *alternate(
+                lambda: F.conv2d(x, wt, None, stride, 1, 1, c),
+                lambda: _C.conv_dw_fwd(x, wt, stride)))
+            row("dgrad", *alternate(
+                lambda: miopen_bwd([True, False, False]),
+                lambda: _C.conv_dw_dgrad(dy, wt, h, h, stride)))
+            cells = []   # (native, MIOpen, spread, cfg), the fastest first
+            for s in (0, 8, 64):
+                tm, tn, sp = alternate(
+                    lambda: miopen_bwd([False, True, False]),
+                    lambda: _C.conv_dw_wgrad(dy, x, stride, s))
+                cells.append((tn, tm, sp, f"splits {s}"))
+            tn, tm, sp, cfg = min(cells)
+            row("wgrad", tm, tn, sp, cfg)
+            del x, wt, y, dy
+
+    # the training step, forward + backward + SGD, tuner off on both sides
+    from mi355x_ddp.models import build_model
+    from mi355x_ddp.ops.conv import MI355Conv2d
+    os.environ["MI355X_AUTOTUNE"] = "0"
+    model = MI355Conv2d.convert(build_model("mobilenet_v1", 100).cuda()) \
+        .to(memory_format=torch.channels_last).train()
+    opt = torch.optim.SGD(model.parameters(), lr=0.01, momentum=0.9)
+    xb = torch.randn(N, 3, args.image_size, args.image_size, device="cuda") \
+        .to(memory_format=torch.channels_last)
+    lb = torch.randint(0, 100, (N,), device="cuda")
+
+    def step(native):
+        os.environ["MI355X_NATIVE_DEPTHWISE"] = native
+        opt.zero_grad(set_to_none=True)
+        with torch.autocast("cuda", dtype=dtype):
+            loss = F.cross_entropy(model(xb).float(), lb)
+        loss.backward()
+        opt.step()
+
+    t0, t1, sp = alternate(lambda: step("0"), lambda: step("1"))
+    print(f"# mobilenet_v1 step, batch {N}, {args.image_size} px: "
+          f"MI355X_NATIVE_DEPTHWISE=0 {t0/1e3:.2f} ms, =1 {t1/1e3:.2f} ms "
+          f"(spread {sp:.1%}), x{t0/t1:.2f}")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=256)
+    p.add_argument("--depthwise", action="store_true",
+                   help="time the depthwise 3x3 layers of MobileNet-v1 at "
+                        "both strides (native depthwise kernels vs MIOpen) "
+                        "and the mobilenet_v1 step with the kernels on and "
+                        "off instead")
     p.add_argument("--grouped", action="store_true",
                    help="time the grouped 3x3 layers of ResNeXt-50 32x4d "
                         "(native grouped kernels vs MIOpen) instead")
@@ -168,6 +270,8 @@ def main():
     print(f"# dtype {args.dtype}, batch {args.batch}")
     if args.grouped:
         return bench_grouped(args, dtype)
+    if args.depthwise:
+        return bench_depthwise(args, dtype)
     N = args.batch
     if args.arch:
         rows = collect_model_shapes(args.arch, args.image_size)
