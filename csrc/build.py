@@ -19,7 +19,8 @@ SOURCES = [os.path.join(REPO, "csrc", "mi355x_kernels.hip"),
            os.path.join(REPO, "csrc", "conv_igemm.hip"),
            os.path.join(REPO, "csrc", "data_aug.hip"),
            os.path.join(REPO, "csrc", "conv_grouped.hip"),
-           os.path.join(REPO, "csrc", "conv_depthwise.hip")]
+           os.path.join(REPO, "csrc", "conv_depthwise.hip"),
+           os.path.join(REPO, "csrc", "se_block.hip")]
 
 
 def out_path() -> str:

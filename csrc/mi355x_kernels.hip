@@ -2698,6 +2698,22 @@ at::Tensor conv_dw_dgrad(at::Tensor dy, at::Tensor w, long H, long W,
 at::Tensor conv_dw_wgrad(at::Tensor dy, at::Tensor x, long stride,
                          long splits);
 
+// csrc/se_block.hip — Squeeze-and-Excitation join, fp32 gate path on MFMA
+at::Tensor se_squeeze(at::Tensor u);
+std::tuple<at::Tensor, at::Tensor> se_excite_fwd(at::Tensor s, at::Tensor w1,
+                                                 at::Tensor b1, at::Tensor w2,
+                                                 at::Tensor b2);
+at::Tensor se_scale_add_relu(at::Tensor u, at::Tensor identity, at::Tensor g);
+at::Tensor se_join_bwd_reduce(at::Tensor dout, at::Tensor out, at::Tensor u);
+std::tuple<at::Tensor, at::Tensor, at::Tensor> se_excite_bwd(
+    at::Tensor dg, at::Tensor g, at::Tensor h, at::Tensor w1, at::Tensor w2);
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> se_excite_wgrad(
+    at::Tensor dz2, at::Tensor h, at::Tensor dz1, at::Tensor s);
+std::tuple<at::Tensor, at::Tensor> se_join_bwd_apply(at::Tensor dout,
+                                                     at::Tensor out,
+                                                     at::Tensor g,
+                                                     at::Tensor ds);
+
 // csrc/data_aug.hip — device-resident input pipeline (crop/flip/normalize)
 std::tuple<at::Tensor, at::Tensor> batch_augment(
     at::Tensor images_u8, at::Tensor labels_i64, at::Tensor idx_i32,
@@ -2777,6 +2793,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dtype; two-stage, no atomics; splits 0=auto",
         py::arg("dy"), py::arg("x"), py::arg("stride") = 1,
         py::arg("splits") = 0);
+  m.def("se_squeeze", &se_squeeze,
+        "s [N, C] fp32 = mean over HW of u (NHWC bf16|fp16, C % 8 == 0)",
+        py::arg("u"));
+  m.def("se_excite_fwd", &se_excite_fwd,
+        "(h, g) = (relu(s W1^T + b1), sigmoid(h W2^T + b2)), all fp32, on "
+        "fp32 MFMA tiles of 16 images",
+        py::arg("s"), py::arg("w1"), py::arg("b1"), py::arg("w2"),
+        py::arg("b2"));
+  m.def("se_scale_add_relu", &se_scale_add_relu,
+        "out = relu(u * g[n, c] + identity)",
+        py::arg("u"), py::arg("identity"), py::arg("g"));
+  m.def("se_join_bwd_reduce", &se_join_bwd_reduce,
+        "dg [N, C] fp32 = sum over HW of (out > 0) * dout * u",
+        py::arg("dout"), py::arg("out"), py::arg("u"));
+  m.def("se_excite_bwd", &se_excite_bwd,
+        "(dz2, dz1, ds) of the two FC layers from dg, all fp32",
+        py::arg("dg"), py::arg("g"), py::arg("h"), py::arg("w1"),
+        py::arg("w2"));
+  m.def("se_excite_wgrad", &se_excite_wgrad,
+        "(dW1, db1, dW2, db2) fp32, contracted over the batch in image order; "
+        "no atomics, bit-reproducible",
+        py::arg("dz2"), py::arg("h"), py::arg("dz1"), py::arg("s"));
+  m.def("se_join_bwd_apply", &se_join_bwd_apply,
+        "(du, d_identity) = (m * dout * g + ds / HW, m * dout), m = out > 0",
+        py::arg("dout"), py::arg("out"), py::arg("g"), py::arg("ds"));
   m.def("bn_stats",&bn_stats, "per-channel sum/sqsum (NCHW)");
   m.def("bn_stats_packed", &bn_stats_packed,
         "per-channel {sum,sqsum} packed [2C], no-atomic NHWC v2");

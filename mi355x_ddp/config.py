@@ -23,7 +23,8 @@ class TrainConfig:
     # model / task
     arch: str = "resnet18"            # resnet18 | resnet34 | resnet50 |
     #   resnext50_32x4d | resnext101_32x8d | resnext50_32x4d_imagenet |
-    #   mobilenet_v1 | mobilenet_v1_imagenet
+    #   mobilenet_v1 | mobilenet_v1_imagenet | se_resnet18 | se_resnet50 |
+    #   se_resnext50_32x4d | se_resnet50_imagenet
     num_classes: int = 100
     image_size: int = 32
 
@@ -156,9 +157,12 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                             "resnet152", "resnet18_imagenet",
                             "resnet50_imagenet", "resnext50_32x4d",
                             "resnext101_32x8d", "resnext50_32x4d_imagenet",
-                            "mobilenet_v1", "mobilenet_v1_imagenet"],
+                            "mobilenet_v1", "mobilenet_v1_imagenet",
+                            "se_resnet18", "se_resnet50",
+                            "se_resnext50_32x4d", "se_resnet50_imagenet"],
                    help="model: the CIFAR-stem ResNets and ResNeXts, their "
-                        "*_imagenet forms for 224 px inputs, or MobileNet-v1 "
+                        "*_imagenet forms for 224 px inputs, the se_* forms "
+                        "with Squeeze-and-Excitation blocks, or MobileNet-v1 "
                         "(mobilenet_v1 for CIFAR, mobilenet_v1_imagenet with "
                         "the stride-2 stem)")
     p.add_argument("--amp", default=None, type=str,

@@ -18,6 +18,7 @@ import torch.nn as nn
 from ..ops import bn_relu, bn_add_relu
 from ..ops.fused_eval import FOLDED_ATTR, conv_bn_act
 from ..ops.pool import GlobalAvgPool2d
+from ..ops.se import SqueezeExcite, se_add_relu
 
 
 def conv_bn(x, conv, bn, relu: bool = True, identity=None):
@@ -61,12 +62,22 @@ def _conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
     return nn.Conv2d(cin, cout, kernel_size=1, stride=stride, bias=False)
 
 
+def _add_se(block, channels: int, se_reduction: int) -> None:
+    """A non-zero `se_reduction` makes `block` a Squeeze-and-Excitation block:
+    it owns `se` and ends with `se_add_relu` on its last BatchNorm's output.
+    At 0 the block has the modules and the forward it always had."""
+    block.se_reduction = se_reduction
+    if se_reduction:
+        block.se = SqueezeExcite(channels, se_reduction)
+
+
 class BasicBlock(nn.Module):
     """Two 3x3 convs; expansion 1 (reference utils/model.py:3-28)."""
 
     expansion = 1
 
-    def __init__(self, cin: int, cout: int, stride: int = 1):
+    def __init__(self, cin: int, cout: int, stride: int = 1,
+                 se_reduction: int = 0):
         super().__init__()
         self.conv1 = _conv3x3(cin, cout, stride)
         self.bn1 = nn.BatchNorm2d(cout)
@@ -78,9 +89,13 @@ class BasicBlock(nn.Module):
                 _conv1x1(cin, cout * self.expansion, stride),
                 nn.BatchNorm2d(cout * self.expansion),
             )
+        _add_se(self, cout * self.expansion, se_reduction)
 
     def forward(self, x):
         out = conv_bn(x, self.conv1, self.bn1)
+        if self.se_reduction:
+            return se_add_relu(conv_bn(out, self.conv2, self.bn2, relu=False),
+                               _identity(self, x), self.se)
         return conv_bn(out, self.conv2, self.bn2,
                        identity=lambda: _identity(self, x))
 
@@ -94,7 +109,8 @@ class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, cin: int, cout: int, stride: int = 1,
-                 groups: int = 1, base_width: int = 64):
+                 groups: int = 1, base_width: int = 64,
+                 se_reduction: int = 0):
         super().__init__()
         width = int(cout * base_width / 64) * groups
         self.conv1 = _conv1x1(cin, width)
@@ -109,10 +125,14 @@ class Bottleneck(nn.Module):
                 _conv1x1(cin, cout * self.expansion, stride),
                 nn.BatchNorm2d(cout * self.expansion),
             )
+        _add_se(self, cout * self.expansion, se_reduction)
 
     def forward(self, x):
         out = conv_bn(x, self.conv1, self.bn1)
         out = conv_bn(out, self.conv2, self.bn2)
+        if self.se_reduction:
+            return se_add_relu(conv_bn(out, self.conv3, self.bn3, relu=False),
+                               _identity(self, x), self.se)
         return conv_bn(out, self.conv3, self.bn3,
                        identity=lambda: _identity(self, x))
 
@@ -120,12 +140,14 @@ class Bottleneck(nn.Module):
 class ResNet(nn.Module):
     def __init__(self, block, num_blocks, num_classes: int = 100,
                  imagenet_stem: bool = False, groups: int = 1,
-                 base_width: int = 64):
+                 base_width: int = 64, se_reduction: int = 0):
         super().__init__()
         self.in_channels = 64
         # ResNeXt (Bottleneck only): passed to every block when not default
         self.block_kwargs = {} if (groups, base_width) == (1, 64) else \
             {"groups": groups, "base_width": base_width}
+        if se_reduction:   # Squeeze-and-Excitation blocks (ops/se.py)
+            self.block_kwargs["se_reduction"] = se_reduction
         if imagenet_stem:
             # standard ImageNet stem: 7x7 s2 + 3x3 s2 maxpool (4x spatial
             # reduction before stage 1) — beyond the reference zoo, for
@@ -237,6 +259,26 @@ def resnext50_32x4d_imagenet(num_classes: int = 100) -> ResNet:
                   groups=32, base_width=4)
 
 
+def se_resnet18(num_classes: int = 100) -> ResNet:
+    """SE-ResNet (Hu et al. 2018) on the CIFAR stem: every block ends with the
+    Squeeze-and-Excitation join of ops/se.py, reduction 16."""
+    return ResNet(BasicBlock, [2, 2, 2, 2], num_classes, se_reduction=16)
+
+
+def se_resnet50(num_classes: int = 100) -> ResNet:
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, se_reduction=16)
+
+
+def se_resnext50_32x4d(num_classes: int = 100) -> ResNet:
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, groups=32,
+                  base_width=4, se_reduction=16)
+
+
+def se_resnet50_imagenet(num_classes: int = 100) -> ResNet:
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, imagenet_stem=True,
+                  se_reduction=16)
+
+
 _FACTORIES = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50,
               "resnet101": resnet101, "resnet152": resnet152,
               "resnet18_imagenet": resnet18_imagenet,
@@ -249,9 +291,15 @@ _RESNEXT_FACTORIES = {"resnext50_32x4d": resnext50_32x4d,
                       "resnext50_32x4d_imagenet": resnext50_32x4d_imagenet}
 
 
+_SE_FACTORIES = {"se_resnet18": se_resnet18, "se_resnet50": se_resnet50,
+                 "se_resnext50_32x4d": se_resnext50_32x4d,
+                 "se_resnet50_imagenet": se_resnet50_imagenet}
+
+
 def build_model(arch: str, num_classes: int = 100) -> nn.Module:
     from .mobilenet import _MOBILENET_FACTORIES
-    factories = {**_FACTORIES, **_RESNEXT_FACTORIES, **_MOBILENET_FACTORIES}
+    factories = {**_FACTORIES, **_RESNEXT_FACTORIES, **_SE_FACTORIES,
+                 **_MOBILENET_FACTORIES}
     if arch not in factories:
         raise ValueError(f"unknown arch {arch!r}; choose from {sorted(factories)}")
     return factories[arch](num_classes)
