@@ -2725,7 +2725,28 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> batch_augment_cutmix(
     at::Tensor lut_f32, long pad, bool channels_last,
     at::ScalarType out_dtype);
 
+// csrc/group_norm.hip — LDS-resident GroupNorm (+ add) (+ ReLU)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> gn_fwd(
+    at::Tensor x, at::Tensor gamma, at::Tensor beta,
+    c10::optional<at::Tensor> residual, long groups, double eps, bool relu);
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> gn_bwd(
+    at::Tensor dy, at::Tensor y, at::Tensor x, at::Tensor mean,
+    at::Tensor rstd, at::Tensor gamma, long groups, bool relu,
+    bool has_residual);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("gn_fwd", &gn_fwd,
+        "(y, mean [N, G], rstd [N, G]) of GroupNorm (+ residual) (+ ReLU) on "
+        "NHWC bf16|fp16 x; fp32 gamma, beta and statistics; one launch",
+        py::arg("x"), py::arg("gamma"), py::arg("beta"),
+        py::arg("residual") = py::none(), py::arg("groups"),
+        py::arg("eps") = 1e-5, py::arg("relu") = true);
+  m.def("gn_bwd", &gn_bwd,
+        "(dx, d_residual | None, dgamma, dbeta); y masks dy when relu; no "
+        "atomics, bit-reproducible",
+        py::arg("dy"), py::arg("y"), py::arg("x"), py::arg("mean"),
+        py::arg("rstd"), py::arg("gamma"), py::arg("groups"),
+        py::arg("relu") = true, py::arg("has_residual") = false);
   m.def("conv_build_wT", &conv_build_wT,
         "build rotated/transposed filter for dgrad (one launch)");
   m.def("conv_fwd_igemm", &conv_fwd_igemm,

@@ -27,6 +27,11 @@ class TrainConfig:
     #   se_resnext50_32x4d | se_resnet50_imagenet
     num_classes: int = 100
     image_size: int = 32
+    # normalization of every arch: "bn" (BatchNorm, SyncBN across ranks) or
+    # "gn" (GroupNorm of min(gn_groups, C // 2) groups on ops/groupnorm.py:
+    # per-sample statistics, so no collective and no running statistics)
+    norm: str = "bn"
+    gn_groups: int = 32
 
     # optimisation (reference defaults: distributed.py:18-25,63-64)
     batch_size: int = 256             # GLOBAL batch, divided by world size
@@ -112,6 +117,10 @@ class TrainConfig:
     max_eval_steps: Optional[int] = None
 
     def __post_init__(self):
+        if self.norm not in ("bn", "gn"):
+            raise ValueError(f"norm must be 'bn' or 'gn', got {self.norm!r}")
+        if self.gn_groups < 1:
+            raise ValueError(f"gn_groups must be >= 1, got {self.gn_groups}")
         if self.hflip and not self.device_data:
             raise ValueError("hflip needs device_data: the DataLoader path "
                              "has no flip and would ignore it silently")
@@ -165,6 +174,14 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                         "with Squeeze-and-Excitation blocks, or MobileNet-v1 "
                         "(mobilenet_v1 for CIFAR, mobilenet_v1_imagenet with "
                         "the stride-2 stem)")
+    p.add_argument("--norm", default=None, type=str, choices=[None, "bn", "gn"],
+                   help="normalization of the --arch model. bn: BatchNorm "
+                        "(default). gn: GroupNorm on the native fused norm + "
+                        "add + ReLU kernels; per-sample statistics, so no "
+                        "SyncBN collectives and no running statistics")
+    p.add_argument("--gn_groups", default=None, type=int,
+                   help="groups of a --norm gn layer (default 32); a layer "
+                        "of C channels gets min(gn_groups, C // 2)")
     p.add_argument("--amp", default=None, type=str,
                    choices=[None, "fp32", "bf16", "fp16", "bf16_o2"],
                    help="precision. fp32: convs on MIOpen. bf16: autocast, "
@@ -274,7 +291,8 @@ def config_from_args(args: argparse.Namespace, **overrides) -> TrainConfig:
     if getattr(args, "fused_eval", False):
         kw["fused_eval"] = True
     for name in ("label_smoothing", "cutmix_alpha", "cutmix_prob",
-                 "lars_eta", "clip_grad_norm", "ema_decay"):
+                 "lars_eta", "clip_grad_norm", "ema_decay", "norm",
+                 "gn_groups"):
         if getattr(args, name, None) is not None:
             kw[name] = getattr(args, name)
     kw.update(overrides)

@@ -70,7 +70,9 @@ def fused_inference(model: nn.Module):
     try:
         if depth == 0:
             for _, bn in conv_bn_pairs(module):
-                if not bn.training and bn.running_mean is not None:
+                # a GroupNorm (norm="gn") has no running statistics either
+                if not bn.training and \
+                        getattr(bn, "running_mean", None) is not None:
                     # a tensor set on a module that is no Parameter and no
                     # registered buffer is a plain attribute: state_dict(),
                     # .to() and the EMA's buffer list do not see it

@@ -52,7 +52,8 @@ def init_seeds(seed: int, deterministic: bool = False,
 def build_training(cfg: TrainConfig, device: torch.device, world_size: int,
                    rank: int, distributed: bool = True, wrap: str = "flat"):
     """Model + criterion + optimizer + scheduler + scaler, wrapped for DP mode."""
-    model = build_model(cfg.arch, cfg.num_classes).to(device)
+    model = build_model(cfg.arch, cfg.num_classes, norm=cfg.norm,
+                        gn_groups=cfg.gn_groups).to(device)
     if cfg.native_ops:
         from ..ops import MI355Conv2d
         from ..ops.pool import MI355MaxPool2d

@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from ..ops import bn_relu, bn_add_relu
 from ..ops.fused_eval import FOLDED_ATTR, conv_bn_act
+from ..ops.groupnorm import convert_group_norm, gn_add_relu, gn_relu
 from ..ops.pool import GlobalAvgPool2d
 from ..ops.se import SqueezeExcite, se_add_relu
 
@@ -38,10 +39,15 @@ def conv_bn(x, conv, bn, relu: bool = True, identity=None):
                 identity = identity()
             return conv_bn_act(x, conv, folded, relu, identity, bn=bn)
     out = conv(x)
+    # a GroupNorm layer (`build_model(..., norm="gn")`) never folds: it has no
+    # running statistics, and runs ops/groupnorm.py in training and evaluation
+    gn = isinstance(bn, nn.GroupNorm)
     if identity is None:
-        return bn_relu(out, bn, relu)
+        return gn_relu(out, bn, relu) if gn else bn_relu(out, bn, relu)
     if callable(identity):
         identity = identity()
+    if gn:
+        return gn_add_relu(out, identity, bn)
     return bn_add_relu(out, identity, bn)
 
 
@@ -296,10 +302,19 @@ _SE_FACTORIES = {"se_resnet18": se_resnet18, "se_resnet50": se_resnet50,
                  "se_resnet50_imagenet": se_resnet50_imagenet}
 
 
-def build_model(arch: str, num_classes: int = 100) -> nn.Module:
+def build_model(arch: str, num_classes: int = 100, norm: str = "bn",
+                gn_groups: int = 32) -> nn.Module:
+    """`norm="gn"` gives the same model with every BatchNorm2d replaced by a
+    GroupNorm of `min(gn_groups, C // 2)` groups (ops/groupnorm.py); the
+    default is the BatchNorm model, module for module."""
     from .mobilenet import _MOBILENET_FACTORIES
     factories = {**_FACTORIES, **_RESNEXT_FACTORIES, **_SE_FACTORIES,
                  **_MOBILENET_FACTORIES}
     if arch not in factories:
         raise ValueError(f"unknown arch {arch!r}; choose from {sorted(factories)}")
-    return factories[arch](num_classes)
+    if norm not in ("bn", "gn"):
+        raise ValueError(f"unknown norm {norm!r}; choose from ['bn', 'gn']")
+    model = factories[arch](num_classes)
+    if norm == "gn":
+        model = convert_group_norm(model, gn_groups)
+    return model

@@ -7,5 +7,6 @@ from .conv import MI355Conv2d, conv2d  # noqa: F401
 from .fused_eval import conv_bn_act, fold_bn  # noqa: F401
 from .pool import GlobalAvgPool2d  # noqa: F401
 from .se import SqueezeExcite, se_add_relu  # noqa: F401
+from .groupnorm import gn_relu, gn_add_relu  # noqa: F401
 from .augment import batch_augment, build_norm_lut, draw_aug_params  # noqa: F401
 from .augment import batch_augment_cutmix, draw_cutmix_params  # noqa: F401
