@@ -20,6 +20,7 @@ SOURCES = [os.path.join(REPO, "csrc", "mi355x_kernels.hip"),
            os.path.join(REPO, "csrc", "data_aug.hip"),
            os.path.join(REPO, "csrc", "conv_grouped.hip"),
            os.path.join(REPO, "csrc", "conv_depthwise.hip"),
+           os.path.join(REPO, "csrc", "conv_depthwise_large.hip"),
            os.path.join(REPO, "csrc", "se_block.hip"),
            os.path.join(REPO, "csrc", "group_norm.hip")]
 

@@ -2698,6 +2698,11 @@ at::Tensor conv_dw_dgrad(at::Tensor dy, at::Tensor w, long H, long W,
 at::Tensor conv_dw_wgrad(at::Tensor dy, at::Tensor x, long stride,
                          long splits);
 
+// csrc/conv_depthwise_large.hip — depthwise KxK convolution, K in {5, 7, 9}
+at::Tensor conv_dwk_fwd(at::Tensor x, at::Tensor w);
+at::Tensor conv_dwk_dgrad(at::Tensor dy, at::Tensor w);
+at::Tensor conv_dwk_wgrad(at::Tensor dy, at::Tensor x, long K, long splits);
+
 // csrc/se_block.hip — Squeeze-and-Excitation join, fp32 gate path on MFMA
 at::Tensor se_squeeze(at::Tensor u);
 std::tuple<at::Tensor, at::Tensor> se_excite_fwd(at::Tensor s, at::Tensor w1,
@@ -2814,6 +2819,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dtype; two-stage, no atomics; splits 0=auto",
         py::arg("dy"), py::arg("x"), py::arg("stride") = 1,
         py::arg("splits") = 0);
+  m.def("conv_dwk_fwd", &conv_dwk_fwd,
+        "depthwise KxK conv forward, K in {5, 7, 9}, stride 1, pad K/2 (NHWC "
+        "bf16|fp16, C % 8 == 0), filter (C, 1, K, K) of any strides",
+        py::arg("x"), py::arg("w"));
+  m.def("conv_dwk_dgrad", &conv_dwk_dgrad,
+        "depthwise KxK conv input-grad on the same filter; dx has dy's "
+        "extents and is written in full",
+        py::arg("dy"), py::arg("w"));
+  m.def("conv_dwk_wgrad", &conv_dwk_wgrad,
+        "depthwise KxK conv weight-grad -> (C, 1, K, K) in the input dtype; "
+        "two-stage, no atomics; splits 0=auto",
+        py::arg("dy"), py::arg("x"), py::arg("K"), py::arg("splits") = 0);
   m.def("se_squeeze", &se_squeeze,
         "s [N, C] fp32 = mean over HW of u (NHWC bf16|fp16, C % 8 == 0)",
         py::arg("u"));

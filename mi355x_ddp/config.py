@@ -24,7 +24,8 @@ class TrainConfig:
     arch: str = "resnet18"            # resnet18 | resnet34 | resnet50 |
     #   resnext50_32x4d | resnext101_32x8d | resnext50_32x4d_imagenet |
     #   mobilenet_v1 | mobilenet_v1_imagenet | se_resnet18 | se_resnet50 |
-    #   se_resnext50_32x4d | se_resnet50_imagenet
+    #   se_resnext50_32x4d | se_resnet50_imagenet | convmixer_256_8 |
+    #   convmixer_256_16 | convmixer_768_32_imagenet
     num_classes: int = 100
     image_size: int = 32
     # normalization of every arch: "bn" (BatchNorm, SyncBN across ranks) or
@@ -168,12 +169,16 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                             "resnext101_32x8d", "resnext50_32x4d_imagenet",
                             "mobilenet_v1", "mobilenet_v1_imagenet",
                             "se_resnet18", "se_resnet50",
-                            "se_resnext50_32x4d", "se_resnet50_imagenet"],
+                            "se_resnext50_32x4d", "se_resnet50_imagenet",
+                            "convmixer_256_8", "convmixer_256_16",
+                            "convmixer_768_32_imagenet"],
                    help="model: the CIFAR-stem ResNets and ResNeXts, their "
                         "*_imagenet forms for 224 px inputs, the se_* forms "
-                        "with Squeeze-and-Excitation blocks, or MobileNet-v1 "
+                        "with Squeeze-and-Excitation blocks, MobileNet-v1 "
                         "(mobilenet_v1 for CIFAR, mobilenet_v1_imagenet with "
-                        "the stride-2 stem)")
+                        "the stride-2 stem), or ConvMixer (convmixer_256_8 "
+                        "and convmixer_256_16 for CIFAR, "
+                        "convmixer_768_32_imagenet for 224 px)")
     p.add_argument("--norm", default=None, type=str, choices=[None, "bn", "gn"],
                    help="normalization of the --arch model. bn: BatchNorm "
                         "(default). gn: GroupNorm on the native fused norm + "

@@ -5,3 +5,6 @@ from .resnet import (ResNet, BasicBlock, Bottleneck, resnet18, resnet34,
                      se_resnet50_imagenet, build_model)  # noqa: F401
 from .mobilenet import (MobileNetV1, DepthwiseSeparable, mobilenet_v1,
                         mobilenet_v1_imagenet)  # noqa: F401
+from .convmixer import (ConvMixer, ConvMixerBlock, convmixer_256_8,
+                        convmixer_256_16,
+                        convmixer_768_32_imagenet)  # noqa: F401

@@ -307,9 +307,10 @@ def build_model(arch: str, num_classes: int = 100, norm: str = "bn",
     """`norm="gn"` gives the same model with every BatchNorm2d replaced by a
     GroupNorm of `min(gn_groups, C // 2)` groups (ops/groupnorm.py); the
     default is the BatchNorm model, module for module."""
+    from .convmixer import _CONVMIXER_FACTORIES
     from .mobilenet import _MOBILENET_FACTORIES
     factories = {**_FACTORIES, **_RESNEXT_FACTORIES, **_SE_FACTORIES,
-                 **_MOBILENET_FACTORIES}
+                 **_MOBILENET_FACTORIES, **_CONVMIXER_FACTORIES}
     if arch not in factories:
         raise ValueError(f"unknown arch {arch!r}; choose from {sorted(factories)}")
     if norm not in ("bn", "gn"):

@@ -52,6 +52,9 @@ out_channels (every depthwise layer of MobileNet-v1) runs on the kernels of
 csrc/conv_depthwise.hip through ``_ConvDepthwise`` (see ``_depthwise_ok`` for
 the scope); ``MI355X_NATIVE_DEPTHWISE=0`` sends it back to torch's conv. The
 kernels read the (C, 1, 3, 3) filter as it is: no shadow and no prep launch.
+A 5x5, 7x7 or 9x9 stride-1 "same" depthwise conv (ConvMixer's) runs on the
+kernels of csrc/conv_depthwise_large.hip through ``_ConvDepthwiseLarge`` (see
+``_depthwise_large_ok``), under the same switch and on the same terms.
 """
 from __future__ import annotations
 
@@ -181,6 +184,35 @@ def _depthwise_ok(x: torch.Tensor, weight: torch.Tensor, stride, padding,
     return x.is_contiguous(memory_format=torch.channels_last)
 
 
+_DEPTHWISE_LARGE_K = (5, 7, 9)
+
+
+def _depthwise_large_ok(x: torch.Tensor, weight: torch.Tensor, stride,
+                        padding, dilation, groups) -> bool:
+    """The large-kernel depthwise kernels (csrc/conv_depthwise_large.hip) take
+    this conv: K x K with K in {5, 7, 9}, stride 1, pad K // 2, dilation 1,
+    channels_last, x and weight in one 16-bit dtype, groups == in_channels ==
+    out_channels == C (a (C, 1, K, K) filter) and C a multiple of 8."""
+    if not native_depthwise_wanted() or not native_conv_wanted() or \
+            not _backend.native_enabled(x):
+        return False
+    if x.dtype not in _NATIVE_DTYPES or weight.dtype != x.dtype:
+        return False
+    if x.dtype == torch.float16 and not native_conv_fp16_wanted():
+        return False
+    if x.dim() != 4 or weight.dim() != 4:
+        return False
+    C, K = x.shape[1], weight.shape[2]
+    if groups != C or weight.shape[0] != C or weight.shape[1] != 1 or \
+            C % 8 != 0:
+        return False
+    if K not in _DEPTHWISE_LARGE_K or weight.shape[3] != K or \
+            tuple(padding) != (K // 2, K // 2) or \
+            tuple(dilation) != (1, 1) or tuple(stride) != (1, 1):
+        return False
+    return x.is_contiguous(memory_format=torch.channels_last)
+
+
 class _Calls:
     """Launch counters of the native grouped passes (one per call of the
     extension function outside the tuner's measurements): lets tests and
@@ -195,6 +227,7 @@ class _Calls:
 
 grouped_calls = _Calls()
 depthwise_calls = _Calls()   # the same for the native depthwise passes
+dwk_calls = _Calls()         # and for the native depthwise KxK passes
 
 
 # --------------------------------------------------------------------------
@@ -360,6 +393,14 @@ def tune_report() -> str:
                     ("auto" if choice[1] == 0 else str(choice[1]))
             else:
                 label = "native depthwise"
+        elif key[0] in ("dwk_fwd", "dwk_dgrad", "dwk_wgrad"):
+            if choice == MIOPEN:   # _ConvDepthwiseLarge
+                label = "MIOpen"
+            elif isinstance(choice, tuple):
+                label = "native depthwise KxK, splits " + \
+                    ("auto" if choice[1] == 0 else str(choice[1]))
+            else:
+                label = "native depthwise KxK"
         else:
             label = _choice_label(choice) if key[0] in ("fwd", "dgrad") \
                 else ("MIOpen" if choice == MIOPEN else str(choice))
@@ -775,6 +816,87 @@ class _ConvDepthwise(torch.autograd.Function):
         return dx, dw, None
 
 
+_DEPTHWISE_LARGE_WGRAD_SPLITS = (0, 64, 512)
+
+
+class _ConvDepthwiseLarge(torch.autograd.Function):
+    """Depthwise K x K stride-1 "same" convolution, K in {5, 7, 9}, on the
+    kernels of csrc/conv_depthwise_large.hip: conv_dwk_fwd, and conv_dwk_dgrad
+    and conv_dwk_wgrad as backward needs them. Each pass is the tuner's choice
+    between the native kernel (default and first candidate) and MIOpen, under
+    the keys "dwk_fwd", "dwk_dgrad" and "dwk_wgrad"; the last also ranges over
+    a few split counts.
+
+    As in `_ConvDepthwise`, `weight` is a 16-bit (C, 1, K, K) tensor of any
+    strides that the kernels read as it is: no prep launch, nothing kept for
+    backward but x and the weight, no WeightShadow (under autocast an fp32
+    parameter is cast per call)."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        x = x.contiguous(memory_format=torch.channels_last)
+        C = _backend.C()
+        ctx.save_for_backward(x, weight)
+        groups, K = x.shape[1], weight.shape[2]
+
+        def run(c):
+            if c == MIOPEN:
+                return F.conv2d(x, weight, None, 1, K // 2, 1, groups)
+            return C.conv_dwk_fwd(x, weight)
+
+        key = _tune_key("dwk_fwd", x.dtype, x.shape, K)
+        choice = _tuned_choice(key, (0, MIOPEN), run, default=0)
+        if choice != MIOPEN:
+            dwk_calls.fwd += 1
+        return run(choice)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        groups, K = x.shape[1], weight.shape[2]
+        C = _backend.C()
+        dx = dw = None
+
+        def miopen(mask):
+            return torch.ops.aten.convolution_backward(
+                dy, x, weight, None, [1, 1], [K // 2, K // 2], [1, 1], False,
+                [0, 0], groups, mask)
+
+        if ctx.needs_input_grad[0]:
+            def run_dx(c):
+                if c == MIOPEN:
+                    return miopen([True, False, False])[0]
+                return C.conv_dwk_dgrad(dy, weight)
+
+            key = _tune_key("dwk_dgrad", x.dtype, dy.shape, K)
+            choice = _tuned_choice(key, (0, MIOPEN), run_dx, default=0)
+            if choice != MIOPEN:
+                dwk_calls.dgrad += 1
+            dx = run_dx(choice)
+        if ctx.needs_input_grad[1]:
+            def run_dw(c):
+                if c == MIOPEN:
+                    return miopen([False, True, False])[1]
+                return C.conv_dwk_wgrad(dy, x, K, c[1])
+
+            key = _tune_key("dwk_wgrad", x.dtype, x.shape, K)
+            choice = _tuned_choice(
+                key, tuple(("splits", s)
+                           for s in _DEPTHWISE_LARGE_WGRAD_SPLITS) +
+                (MIOPEN,), run_dw, default=("splits", 0))
+            if choice != MIOPEN:
+                dwk_calls.wgrad += 1
+            dw = run_dw(choice)
+            # the stride fix-up of _ConvDepthwise.backward: on (C, 1, K, K)
+            # the contiguous and the channels_last strides name one order
+            if dw.stride() != weight.stride() and dw.is_contiguous() and (
+                    weight.is_contiguous() or weight.is_contiguous(
+                        memory_format=torch.channels_last)):
+                dw = dw.as_strided(weight.shape, weight.stride())
+        return dx, dw
+
+
 def conv2d(x: torch.Tensor, weight: torch.Tensor, stride=(1, 1),
            padding=(0, 0), dilation=(1, 1), groups: int = 1) -> torch.Tensor:
     if _native_ok(x, weight, stride, padding, dilation, groups):
@@ -783,6 +905,8 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, stride=(1, 1),
         return _ConvGrouped.apply(x, weight, stride[0], groups)
     if _depthwise_ok(x, weight, stride, padding, dilation, groups):
         return _ConvDepthwise.apply(x, weight, stride[0])
+    if _depthwise_large_ok(x, weight, stride, padding, dilation, groups):
+        return _ConvDepthwiseLarge.apply(x, weight)
     return F.conv2d(x, weight, None, stride, padding, dilation, groups)
 
 

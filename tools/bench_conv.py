@@ -239,8 +239,96 @@ def bench_depthwise(args, dtype):
           f"(spread {sp:.1%}), x{t0/t1:.2f}")
 
 
+# The depthwise K x K layers of the ConvMixer models: (name, N, C, H, K).
+CONVMIXER_DW_LAYERS = [("256_8", 256, 256, 16, 5), ("256_16", 256, 256, 32, 9),
+                       ("768_32", 64, 768, 32, 7)]
+
+
+def bench_depthwise_large(args, dtype):
+    """Native depthwise K x K kernels against MIOpen, per pass, at the
+    ConvMixer layer shapes (each at its own batch), alternating window by
+    window as `bench_depthwise` does. GF/s is 2 K^2 flops per element and GB/s
+    the compulsory traffic (one read and one write of an activation), both
+    over the native time. Then the convmixer_256_8 training step at --batch
+    with MI355X_NATIVE_DEPTHWISE=1 against =0."""
+    from mi355x_ddp import _C
+    kw = dict(warmup=args.warmup, iters=args.iters)
+
+    def alternate(fa, fb):
+        ta, tb = [], []
+        for _ in range(args.windows):
+            ta.append(timeit(fa, **kw))
+            tb.append(timeit(fb, **kw))
+        ta.sort(), tb.sort()
+        m = len(ta) // 2
+        return ta[m], tb[m], (tb[-1] - tb[0]) / tb[m]
+
+    print(f"{'shape':>22} {'pass':>6} {'MIOpen us':>10} {'native us':>10} "
+          f"{'spread':>7} {'cfg':>10} {'x':>6} {'GF/s':>8} {'GB/s':>7}")
+    for name, n, c, h, k in CONVMIXER_DW_LAYERS:
+        x = torch.randn(n, c, h, h, device="cuda", dtype=dtype) \
+            .to(memory_format=torch.channels_last)
+        wt = torch.randn(c, 1, k, k, device="cuda", dtype=dtype) / k
+        dy = torch.randn_like(x)
+        flops, nbytes = 2.0 * k * k * x.numel(), 4.0 * x.numel()
+
+        def miopen_bwd(mask):
+            return torch.ops.aten.convolution_backward(
+                dy, x, wt, None, [1, 1], [k // 2, k // 2], [1, 1], False,
+                [0, 0], c, mask)
+
+        def row(pss, tm, tn, spread, cfg=""):
+            print(f"{f'{name} {n}x{c}x{h}x{h} k{k}':>22} {pss:>6} {tm:10.1f} "
+                  f"{tn:10.1f} {spread:7.1%} {cfg:>10} {tm/tn:6.2f} "
+                  f"{flops/tn/1e3:8.0f} {nbytes/tn/1e3:7.1f}", flush=True)
+
+        row("fwd", *alternate(
+            lambda: F.conv2d(x, wt, None, 1, k // 2, 1, c),
+            lambda: _C.conv_dwk_fwd(x, wt)))
+        row("dgrad", *alternate(lambda: miopen_bwd([True, False, False]),
+                                lambda: _C.conv_dwk_dgrad(dy, wt)))
+        cells = []   # (native, MIOpen, spread, cfg), the fastest first
+        for s in (0, 64, 512):
+            tm, tn, sp = alternate(lambda: miopen_bwd([False, True, False]),
+                                   lambda: _C.conv_dwk_wgrad(dy, x, k, s))
+            cells.append((tn, tm, sp, f"splits {s}"))
+        tn, tm, sp, cfg = min(cells)
+        row("wgrad", tm, tn, sp, cfg)
+        del x, wt, dy
+
+    # the training step, forward + backward + SGD, tuner off on both sides
+    from mi355x_ddp.models import build_model
+    from mi355x_ddp.ops.conv import MI355Conv2d
+    os.environ["MI355X_AUTOTUNE"] = "0"
+    N = args.batch
+    model = MI355Conv2d.convert(build_model("convmixer_256_8", 100).cuda()) \
+        .to(memory_format=torch.channels_last).train()
+    opt = torch.optim.SGD(model.parameters(), lr=0.01, momentum=0.9)
+    xb = torch.randn(N, 3, 32, 32, device="cuda") \
+        .to(memory_format=torch.channels_last)
+    lb = torch.randint(0, 100, (N,), device="cuda")
+
+    def step(native):
+        os.environ["MI355X_NATIVE_DEPTHWISE"] = native
+        opt.zero_grad(set_to_none=True)
+        with torch.autocast("cuda", dtype=dtype):
+            loss = F.cross_entropy(model(xb).float(), lb)
+        loss.backward()
+        opt.step()
+
+    t0, t1, sp = alternate(lambda: step("0"), lambda: step("1"))
+    print(f"# convmixer_256_8 step, batch {N}, 32 px: "
+          f"MI355X_NATIVE_DEPTHWISE=0 {t0/1e3:.2f} ms, =1 {t1/1e3:.2f} ms "
+          f"(spread {sp:.1%}), x{t0/t1:.2f}")
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--depthwise-large", action="store_true",
+                   help="time the depthwise 5x5 / 7x7 / 9x9 layers of the "
+                        "ConvMixer models (native depthwise KxK kernels vs "
+                        "MIOpen) and the convmixer_256_8 step with the "
+                        "kernels on and off instead")
     p.add_argument("--batch", type=int, default=256)
     p.add_argument("--depthwise", action="store_true",
                    help="time the depthwise 3x3 layers of MobileNet-v1 at "
@@ -272,6 +360,8 @@ def main():
         return bench_grouped(args, dtype)
     if args.depthwise:
         return bench_depthwise(args, dtype)
+    if args.depthwise_large:
+        return bench_depthwise_large(args, dtype)
     N = args.batch
     if args.arch:
         rows = collect_model_shapes(args.arch, args.image_size)
